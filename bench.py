@@ -11,10 +11,14 @@ identification map.  With N ranks every rank processes its own tiles (weak scali
 per-barcode counts are summed on each rank and all-reduced over RCCL once, after the timed
 steps -- the path's only exchange (collect_measurement_results.py:92-98 across FOVs).
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-extras]
-At N=1 the line also carries "extras": the other configurations of BASELINE.json measured the
-same way (cfg3 with the f32-MFMA classifier and without the per-pixel GEMM; cfg2 synthetic-
-community tiles against the 127-barcode library with the NL-means roofline; cfg4 the biofilm
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                [--full [--no-cpu-baseline] [--no-extras]]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step returned
+(dump_outputs below).  Everything else is measured only with --full: "roofline" (the per-pixel
+classifier isolated after the timed region), "cpu_baseline" (the restatement on the host cores)
+and, at N=1, "extras": the other configurations of BASELINE.json measured the same way
+(cfg3 with the f32-MFMA classifier and without the per-pixel GEMM; cfg2 synthetic-community tiles against the 127-barcode library with the NL-means roofline; cfg4 the biofilm
 volume chain from a 1024x1024x64x63 stack with the enhance3d roofline; the streaming kernels
 against HBM).  With --gpus N > 1 and no torch.distributed environment (WORLD_SIZE unset) bench.py
 starts torch.distributed.run itself -- N fresh worker processes, one per GPU, before anything
@@ -547,6 +551,62 @@ def _self_launch(n):
     return subprocess.call(launch_cmd(n, sys.argv[1:], _free_port()), cwd=REPO)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20190101
+DUMP_SAMPLE_PX = 1 << 17     # pixels of every map written per tile
+
+
+def dump_outputs(dirname, results, counts):
+    """--dump-outputs: what the timed path returned in its last step, as dirname/<name>.npy.
+
+    results: the TileResult of every tile of the last timed step (one per concurrent slot, in slot
+    order); counts: the per-barcode counts summed over all timed tiles (all-reduced over the
+    ranks).  Written per slot j as tile<j>_<name>: the per-cell rows in full (labels, avgint,
+    avgint_norm, cell_idx, cell_dist) and the tile's barcode counts; of the four (H, W) maps
+    (segmentation, identification, pixel_idx, pixel_dist) the same fixed, seeded sample of
+    DUMP_SAMPLE_PX pixels (sample_px holds their flat indices), fewer when the slots would not
+    fit: at most DUMP_MAX_BYTES are written in all.  Floating-point arrays keep their precision
+    (f32 / f64); integer arrays are written as f64, which holds every value they take exactly.
+    The inputs are seeded, so two runs with the same arguments write the same arrays: bit for bit,
+    but for the f64 per-cell sums (avgint, avgint_norm, cell_dist), whose accumulation order is the
+    device's and which agree to ~1e-15."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    written = [0]
+
+    def put(name, t):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        written[0] += a.nbytes
+        if written[0] > DUMP_MAX_BYTES:
+            raise RuntimeError("--dump-outputs: %s would pass %d bytes" % (name, DUMP_MAX_BYTES))
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+    torch.cuda.synchronize()
+    put("counts", counts)
+    results = [r for r in results if r is not None]
+    if not results:
+        return
+    # three maps as f64 and one f32 per sampled pixel; half of the limit is left to the per-cell rows
+    npx = min(H * W, DUMP_SAMPLE_PX, DUMP_MAX_BYTES // 2 // (28 * len(results)))
+    sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=npx, replace=False))
+    put("sample_px", sample)
+    sel = torch.from_numpy(sample).to(results[0].counts.device)
+    for j, r in enumerate(results):
+        m = r.meas
+        rows = {"counts": r.counts, "labels": m.labels, "avgint": m.avgint, "avgint_norm": m.avgint_norm,
+                "cell_idx": r.cell_idx, "cell_dist": r.cell_dist}
+        maps = {"segmentation": m.segmentation, "identification": r.identification,
+                "pixel_idx": r.pixel_idx, "pixel_dist": r.pixel_dist}
+        for name, t in rows.items():
+            put("tile%d_%s" % (j, name), t)
+        for name, t in maps.items():
+            if t is not None:                     # --no-per-pixel: no per-pixel maps
+                put("tile%d_%s" % (j, name), t.reshape(-1)[sel])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -555,9 +615,14 @@ def main():
     ap.add_argument("--tiles", type=int, default=0, help="distinct resident tiles per rank (default 2*concurrent)")
     ap.add_argument("--concurrent", type=int, default=6,
                     help="tiles processed concurrently per step per rank (DESIGN.md 'Concurrency on one GPU')")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the classifier roofline, the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the results of its last timed step as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-per-pixel", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg2 / cfg3-variant / cfg4 measurements")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the cfg2 / cfg3-variant / cfg4 measurements")
     ap.add_argument("--no-overlap", action="store_true",
                     help="run the per-pixel classification after the segmentation on one stream")
     ap.add_argument("--dump-counts", default=None, help="rank 0 writes the all-reduced barcode counts (.npy)")
@@ -669,7 +734,7 @@ def main():
         counts = outs[0][1]
         for _, a in outs[1:]:
             counts = counts + a
-        return outs[-1][0], counts
+        return [r for r, _ in outs], counts
 
     if rank == 0:
         _progress("%d tiles resident; warm-up" % len(tiles))
@@ -678,7 +743,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res, counts = run(args.warmup, args.steps, True)
+    last, counts = run(args.warmup, args.steps, True)
+    res = last[-1]
     if world > 1:
         if backend == "nccl":
             P.allreduce_counts(counts)      # global per-barcode counts of the whole batch
@@ -694,6 +760,8 @@ def main():
     total_cells = int(counts.sum().item())
     if args.dump_counts and rank == 0:
         np.save(args.dump_counts, counts.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, counts)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -721,7 +789,7 @@ def main():
     }
     if world > 1 and backend != "nccl":
         out["config"]["dist_backend"] = backend
-    if per_pixel and ev:
+    if args.full and per_pixel and ev:
         from hiprfish_image_analysis_amd import kernels as K
         ms_in = float(np.mean([a.elapsed_time(b) for a, b in ev]))
         # The classifier's own efficiency: the same launch alone on its stream after the timed
@@ -800,9 +868,9 @@ def main():
                                 "note": "mean launch time on the classifier's side stream inside the timed region "
                                         "(HIP events), where %d tiles are in flight and the segmentation streams run "
                                         "at higher priority: overlap, not kernel work" % T}}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         out["extras"] = _extras(dev, T, streams, pool, tiles, lib)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = _cpu_baseline(ref, bounds)
     if rank == 0:
         print(json.dumps(out), flush=True)

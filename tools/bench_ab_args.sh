@@ -12,7 +12,7 @@ for rep in $(seq $reps); do
     for w in $a; do
       if [ ${#args[@]} -eq 0 ] && [[ $w =~ ^[A-Z_][A-Z0-9_]*= ]]; then envs+=("$w"); else args+=("$w"); fi
     done
-    r=$(env HRF_NONE=1 "${envs[@]}" timeout -k 10 240 python3 bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 5 "${args[@]}" 2>/dev/null) || exit 1
+    r=$(env HRF_NONE=1 "${envs[@]}" timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 5 "${args[@]}" 2>/dev/null) || exit 1
     echo "[$a] $(echo "$r" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d.get("roofline", {}).get("kernel_ms"))')" >> $out
   done
 done

@@ -9,7 +9,7 @@ reps=$1; shift
 for rep in $(seq $reps); do
   for e in "$@"; do
     ev=$e; [ "$e" = "-" ] && ev="HRF_NONE=1"
-    r=$(env $ev timeout -k 10 240 python3 bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 5 2>/dev/null) || exit 1
+    r=$(env $ev timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 5 2>/dev/null) || exit 1
     echo "[$e] $(echo "$r" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d.get("roofline", {}).get("kernel_ms"))')" >> $out
   done
 done

@@ -15,9 +15,9 @@ rc=$?
 tail -3 $o/pytest_gpu.txt
 case $rc in 0|1) ;; *) echo "test run ended with status $rc"; exit 1;; esac
 fi
-timeout -k 10 600 python -u bench.py > $o/bench.json 2> $o/bench.err || { echo "bench failed"; tail -30 $o/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $o/bench.json 2> $o/bench.err || { echo "bench failed"; tail -30 $o/bench.err; exit 1; }
 cut -c1-300 $o/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o run -- python3 bench.py --steps 30 --warmup 5 --no-extras --no-cpu-baseline > $o/prof_bench.json 2> $o/prof.err || { echo "profile failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o run -- python3 bench.py --steps 30 --warmup 5 --full --no-extras --no-cpu-baseline > $o/prof_bench.json 2> $o/prof.err || { echo "profile failed"; exit 1; }
 bash tools/gpu_pmc.sh $tag t || { echo "pmc failed"; exit 1; }
 bash tools/gpu_pmc_hbm.sh || { echo "pmc hbm failed"; exit 1; }
 bash tools/gpu_pmc_nlm.sh $tag || { echo "pmc nlm failed"; exit 1; }
