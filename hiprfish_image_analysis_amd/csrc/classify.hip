@@ -81,7 +81,8 @@ constexpr int RCH = 64;  // references per LDS chunk (prefetched into registers)
 struct ExactHdr {
   int32_t R, C, nseg, idx0;  // idx0 / D0: the all-zero pixel's argmin and distance
   double D0;
-  int32_t tiny;              // some row has 0 < ny < 1e-30: the list kernel's f32 pass is not safe
+  int32_t tiny;              // some row has 0 < ny < 1e-30, ny >= 1e30 or a non-finite ny: the list
+                             // kernel's f32 pass is not safe (underflow / overflow of its raw products)
   float zero[4];             // 0: what an uncovered pixel's channel reads (a load that needs no branch)
 };
 struct ExactLayout {
@@ -147,7 +148,9 @@ __global__ void exact_hdr_kernel(const double *__restrict__ ny, int32_t R, int32
     for (int sg = 0; sg < nseg; ++sg) {
       const double v = ny[(int64_t)r * nseg + sg];
       sum += v == 0.0 ? 0.0 : 1.0;
-      tiny |= (v > 0.0 && v < 1e-30) ? 1 : 0;
+      // the pixel side's gate (refine_list_kernel: v < 1e-30 || v > 1e30) on the library; the
+      // negated compare also takes NaN and inf
+      tiny |= ((v > 0.0 && v < 1e-30) || !(v < 1e30)) ? 1 : 0;
     }
     const double d = sum / nseg;
     if (d < best) {
@@ -415,6 +418,16 @@ __device__ __forceinline__ void refine_pixels64(const RefineArgs &A, int C, cons
 
 
 
+// A library segment the screens can normalise: a finite, non-zero sum of squares nn.  A segment
+// holding a NaN or an inf (nn is then NaN or inf; finite f32 values cannot overflow the f64 sum)
+// is written to the MFMA tables as an all-zero segment with its zero-segment indicator set, so no
+// NaN reaches a screen's argmax.  Its screen term is then 1 against a pixel's all-zero segment
+// (restated: 0, the one-zero case) and 0 against any other (restated: a NaN distance, which never
+// wins): the screen over-scores such a row and never under-scores it, so the certificate's
+// premise -- no other row's restated score above the runner-up bound -- holds, and the exact
+// section keeps the raw values for the f64 passes.
+__device__ __forceinline__ bool seg_live(double nn) { return nn > 0.0 && nn < __builtin_inf(); }
+
 // refx[r][0..C) = ref / |ref_seg| (0 if the norm is 0), refx[r][C+s] = (norm_s == 0),
 // zero padding to KP columns and to Rpad rows.
 __global__ void ref_prep_kernel(const float *__restrict__ ref, int32_t R, int32_t C, Bounds bd, int32_t KP,
@@ -428,9 +441,10 @@ __global__ void ref_prep_kernel(const float *__restrict__ ref, int32_t R, int32_
   for (int s = 0; s < bd.nseg; ++s) {
     double nn = 0.0;
     for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) nn += (double)x[c] * (double)x[c];
-    const double inv = nn > 0 ? 1.0 / sqrt(nn) : 0.0;
-    for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) o[c] = (float)((double)x[c] * inv);
-    o[C + s] = nn > 0 ? 0.0f : 1.0f;
+    const bool live = seg_live(nn);
+    const double inv = live ? 1.0 / sqrt(nn) : 0.0;
+    for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) o[c] = live ? (float)((double)x[c] * inv) : 0.0f;
+    o[C + s] = live ? 0.0f : 1.0f;
   }
 }
 
@@ -608,14 +622,15 @@ __global__ void ref_prep_f16_kernel(const float *__restrict__ ref, int32_t R, in
   for (int s = 0; s < bd.nseg; ++s) {
     double nn = 0.0;
     for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) nn += (double)x[c] * (double)x[c];
-    const double inv = nn > 0 ? 1.0 / sqrt(nn) : 0.0;
+    const bool live = seg_live(nn);
+    const double inv = live ? 1.0 / sqrt(nn) : 0.0;
     for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) {
-      const float v = (float)((double)x[c] * inv);
+      const float v = live ? (float)((double)x[c] * inv) : 0.0f;
       const _Float16 h = (_Float16)v;
       hi[c] = h;
       lo[c] = (_Float16)(v - (float)h);
     }
-    hi[C + s] = (_Float16)(nn > 0 ? 0.0f : 1.0f);
+    hi[C + s] = (_Float16)(live ? 0.0f : 1.0f);
   }
 }
 
@@ -1364,14 +1379,18 @@ __device__ __forceinline__ void sweep_w16(const char *__restrict__ gref, char *l
         t2[g] = med3i(t1[g], t2[g], k3);
         t1[g] = max(t1[g], k3);
       } else {
+        // row by row, the runner-up before the best: min(best, s) is the loser of each compare, so
+        // the runner-up also sees two rows of this lane's own four (rows 4Q + i of the block).
+        // Taking the four runner-up updates first lost exactly those: a near-duplicate pair in
+        // adjacent rows was then certified on the first of the two.
 #pragma unroll
-        for (int i = 0; i < 4; ++i) sec[g] = fmaxf(sec[g], fminf(best[g], pv[g][i]));
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) {
+          sec[g] = fmaxf(sec[g], fminf(best[g], pv[g][i]));
           if (pv[g][i] > best[g]) {
             best[g] = pv[g][i];
             bi[g] = pr + i;
           }
+        }
       }
     }
     if (KEYED && g1 == NG && pb == NB - 1) {
@@ -1664,14 +1683,15 @@ __global__ void ref_prep_lay_kernel(const float *__restrict__ ref, int32_t R, in
   for (int s = 0; s < bd.nseg; ++s) {
     double nn = 0.0;
     for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) nn += (double)x[c] * (double)x[c];
-    const double inv = nn > 0 ? 1.0 / sqrt(nn) : 0.0;
+    const bool live = seg_live(nn);
+    const double inv = live ? 1.0 / sqrt(nn) : 0.0;
     for (int c = bd.b[s]; c < bd.b[s + 1]; ++c) {
-      const float v = (float)((double)x[c] * inv);
+      const float v = live ? (float)((double)x[c] * inv) : 0.0f;
       const _Float16 h = (_Float16)v;
       hi[c] = h;
       lo[c] = (_Float16)(v - (float)h);
     }
-    if (!(nn > 0)) hi[2 * KP + s] = (_Float16)1.0f;
+    if (!live) hi[2 * KP + s] = (_Float16)1.0f;
   }
 }
 
@@ -2065,6 +2085,12 @@ __global__ __launch_bounds__(LIST_NT) void refine_list_kernel(PixSrc S, int32_t 
       if (lane == 0) {
         float th = mx - (float)(2.0 * eps32) * 1.0001f;
         thrb[j] = th - fabsf(th) * 1e-6f;  // the subtraction's own rounding, generously
+        // an overflowed f32 pass (mx +inf: the threshold is NaN and no row meets it) would answer
+        // row 0 at distance inf: every row of such a pixel is scored exactly instead.  With the
+        // pixel's and the library's range gates (sums of squares <= 1e30 both: no partial sum of a
+        // segment's products passes sqrt(nx ny) <= 1e30) the pass cannot overflow; this is the
+        // guard behind them.
+        if (!(fabsf(thrb[j]) < __builtin_inff())) atomicOr(&fullb[j], 1);
       }
     }
     __syncthreads();

@@ -52,6 +52,7 @@ struct hrf_tile_ctx {
   uint8_t *flags = nullptr;
   void *rwork = nullptr;        // the refine's list (hrf_classify_refine_work_bytes)
   int64_t rwork_bytes = 0;
+  bool pix_ran = false;         // the last tile ran the per-pixel classifier (rwork holds its count)
   // per-label buffers, grown on demand (capacity cap labels + 1)
   int64_t cap = 0;
   double *sums = nullptr;
@@ -185,6 +186,11 @@ hrf_status hrf_tile_ctx_destroy(hrf_tile_ctx *t) {
 
 hrf_status hrf_tile_ctx_pixel_listed(hrf_tile_ctx *t, int32_t *n_host) {
   HRF_REQUIRE(t && n_host, "tile_ctx_pixel_listed: bad arguments");
+  *n_host = 0;
+  if (!t->pix_ran) return HRF_OK;  // no tile yet, or the last one had per_pixel = 0: nothing was listed
+  // the count is written on the tile's side stream, which may be a non-blocking one the null
+  // stream's copy does not wait for
+  HRF_HIP(hipDeviceSynchronize());
   HRF_HIP(hipMemcpy(n_host, t->rwork, sizeof(int32_t), hipMemcpyDeviceToHost));
   return HRF_OK;
 }
@@ -208,6 +214,7 @@ hrf_status hrf_tile_ecoli(hrf_tile_ctx *t, const float *const *lasers_host, cons
   hipStream_t s = (hipStream_t)stream;
   hipStream_t side = side_stream ? (hipStream_t)side_stream : s;
   const int64_t H = t->H, W = t->W, n = H * W;
+  t->pix_ran = false;  // until this tile's classifier is queued (hrf_tile_ctx_pixel_listed)
   // ecoli :45-57 shifts of the channel-max projections, on the device
   double *proj[NL];
   for (int l = 0; l < NL; ++l) proj[l] = t->proj + l * n;
@@ -238,6 +245,7 @@ hrf_status hrf_tile_ecoli(hrf_tile_ctx *t, const float *const *lasers_host, cons
     // (hrf_classify_pixels_table_exact)
     HRF_TRY(hrf_classify_pixels_table_exact(t->table, t->flags, lasers_host, CH, t->shifts, NL, H, W, 1, refx, R,
                                             BOUNDS, NL, pixel_idx, pixel_dist, t->rwork, t->rwork_bytes, side));
+    t->pix_ran = true;
     if (pix_end) HRF_HIP(hipEventRecord((hipEvent_t)pix_end, side));
     if (side != s) HRF_HIP(hipEventRecord(t->ev_pix, side));
   }

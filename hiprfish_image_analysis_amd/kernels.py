@@ -822,7 +822,12 @@ def _check_refx(refx, R, C, bounds, mode, where):
 
 def classify_pixels(stack, refx, R, bounds, mode=None):
     """per-pixel classification, exact: the restatement's argmin (lowest row on ties) and its
-    f64 distance rounded to f32 (hrf_classify_pixels = MFMA screen + f64 refine)"""
+    f64 distance rounded to f32 (hrf_classify_pixels = MFMA screen + f64 refine).
+
+    The library the answer is exact against is the F32 one classify_prepare was given, promoted to
+    f64 -- not an f64 library it was rounded from (classify_cells reads f64 rows as given).
+    Limits: R <= 4096 rows, C <= 128 channels, and stack.numel() = H * W * C < 2^31 (the refine
+    indexes the pixels with 32-bit element offsets); ValueError otherwise."""
     stack = _dev(stack, torch.float32, "stack")
     C = stack.shape[-1]
     if mode is None:
@@ -1238,7 +1243,8 @@ def tile_stats(device, H, W):
 
 def tile_pixel_listed(device, H, W):
     """pixels of the last native tile whose per-pixel certificate failed (scored in full by the
-    refine's list pass); synchronises"""
+    refine's list pass); 0 when that tile ran without the per-pixel classifier; synchronises the
+    device"""
     import ctypes
     n = ctypes.c_int32(0)
     with _TILE_CTX.use(device, H, W) as ctx:

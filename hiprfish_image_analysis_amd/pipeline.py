@@ -272,6 +272,10 @@ class Library:
         return self.spectra.shape[0]
 
     def refx(self):
+        """the per-pixel classifier's prepared library.  It is made from spectra ROUNDED TO F32:
+        per pixel the answers are exact against spectra.to(float32), not against the f64 rows
+        (which the per-cell classifier reads as they are).  R <= 4096, C <= 128; a tile must hold
+        H * W * C < 2^31 values (kernels.classify_pixels)."""
         if self._refx is None:
             self._refx = K.classify_prepare(self.spectra.to(torch.float32), self.bounds)
         return self._refx

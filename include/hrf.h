@@ -374,7 +374,8 @@ HRF_API hrf_status hrf_tile_ctx_destroy(hrf_tile_ctx *ctx);
 /* the segmentation context the tile context runs (hrf_seg_ctx_stats of the last tile) */
 HRF_API hrf_status hrf_tile_ctx_seg(hrf_tile_ctx *ctx, hrf_seg_ctx **seg);
 /* pixels of the last tile the per-pixel certificate did not settle (scored in full by the refine's
- * list pass); synchronises with the device */
+ * list pass); 0 before the first tile and after a tile run with per_pixel = 0.  Synchronises the
+ * whole device (the count is written on the tile's side stream). */
 HRF_API hrf_status hrf_tile_ctx_pixel_listed(hrf_tile_ctx *ctx, int32_t *n_host);
 HRF_API hrf_status hrf_tile_ecoli(hrf_tile_ctx *ctx, const float *const *lasers_host, const float *cal,
                                   const void *refx, const double *lib, const double *lib_flags, int32_t R,
@@ -436,6 +437,14 @@ HRF_API hrf_status hrf_classify_geometry(int32_t C, int32_t nseg, int32_t R, int
  * pad 16 B, or 32 B for mode 2 on the E. coli layout) */
 HRF_API hrf_status hrf_classify_table_row_bytes(int32_t C, const int32_t *bounds_host, int32_t nseg, int32_t mode,
                                                 int32_t *row_bytes_host);
+/* THE PER-PIXEL LIBRARY IS F32: ref holds the library rounded to f32, and every per-pixel entry
+ * point below is exact against THOSE values promoted to f64 -- not against an f64 library they
+ * were rounded from (the per-cell classifier, hrf_classify_cells, reads f64 rows as given).
+ * Limits: R <= 4096 and C <= 128 (HRF_EINVAL otherwise); the refine indexes a pixel source with
+ * 32-bit element offsets, so H * W * C < 2^31 per call (HRF_EINVAL otherwise).  Any finite row
+ * values are exact, whatever their scale (huge, tiny, subnormal, zero or negative); a row holding
+ * NaN or inf behaves as in the restatement: its distance is NaN wherever the pixel's segment is
+ * not all zero, so it is never the answer there. */
 HRF_API hrf_status hrf_classify_prepare_refs(const float *ref, int32_t R, int32_t C, const int32_t *bounds_host,
                                              int32_t nseg, int32_t mode, void *refx, hrf_stream_t stream);
 /* bytes of the prepared library of `mode` for R rows: the MFMA table (rpad rows of
