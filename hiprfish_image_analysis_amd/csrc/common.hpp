@@ -104,7 +104,7 @@ hrf_status kmeans_1d_sorted_pair_deferred(const double *x, int64_t n, int32_t k1
                                           void *work, int64_t work_bytes, hipStream_t s, int32_t *err_pinned);
 const int32_t *kmeans_error_flag(void *work, int64_t n);
 
-// the per-cell tail with device-held row counts (classify.hip, stats.hip; used by tile.hip)
+// the per-cell tail with device-held row counts (classify_cells.hip, stats.hip; used by tile.hip)
 hrf_status cells_lib_prep(const double *a, int32_t R, int32_t C, const int32_t *bounds_host, int32_t nseg, double *t,
                           double *ny, hipStream_t s);
 hrf_status segment_flags_devn(const double *x, int64_t nmax, const int32_t *nrows_dev, int32_t C,

@@ -6,7 +6,7 @@
 // anyway, stack.hip) or by a standalone pass, writes the operands in the exact register layout of
 // the 16x16x32 MFMA B operand: per group of 16 pixels, per k-block t and hi/lo half, one 1 KiB
 // block of 64 lanes x 16 B (lane = pixel (lane & 15), columns 32t + 8 (lane >> 4) .. + 7), so the
-// classifier's prologue is 2 KT global_load_dwordx4 per group (classify.hip
+// classifier's prologue is 2 KT global_load_dwordx4 per group (classify_screen.hip
 // classify_pixels_w16t_kernel) and the sweep starts as soon as they land.  A flag byte per pixel
 // carries its all-zero segments (bits 0..4) and "has a negative value" (bit 7).  Bit-identical to
 // the in-kernel build: same f32 sums in channel order, same v_rsq, same f64 redo on underflow.

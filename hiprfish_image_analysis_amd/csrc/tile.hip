@@ -240,9 +240,10 @@ hrf_status hrf_tile_ecoli(hrf_tile_ctx *t, const float *const *lasers_host, cons
       HRF_HIP(hipStreamWaitEvent(side, t->ev_reg, 0));
     }
     if (pix_start) HRF_HIP(hipEventRecord((hipEvent_t)pix_start, side));
-    // the split-fp16 screen from the assembly's table with its exact f64 refine fused in, reading
-    // the pixels from the five shifted acquisitions, then the list pass
-    // (hrf_classify_pixels_table_exact)
+    // the split-fp16 screen from the assembly's table, then the f64 certificate as a kernel of its
+    // own (reading the pixels from the five shifted acquisitions), then the list pass
+    // (hrf_classify_pixels_table_exact: the two-kernel form, faster than the fused one beside
+    // concurrent tiles)
     HRF_TRY(hrf_classify_pixels_table_exact(t->table, t->flags, lasers_host, CH, t->shifts, NL, H, W, 1, refx, R,
                                             BOUNDS, NL, pixel_idx, pixel_dist, t->rwork, t->rwork_bytes, side));
     t->pix_ran = true;

@@ -321,7 +321,8 @@ def classify_cells(avgint_norm: torch.Tensor, lib: Library, variant: int = 0, fl
 
 def classify_pixels(stack: torch.Tensor, lib: Library):
     """north_star per-pixel mode: argmin over the library of the ungated segmented-cosine
-    distance for every pixel spectrum (one fused f32-MFMA GEMM + argmax)."""
+    distance for every pixel spectrum (a split-fp16 MFMA screen with a fused argmax, then the f64
+    certificate and list pass: the restatement's exact answer)."""
     return K.classify_pixels(stack, lib.refx(), lib.R, lib.bounds)
 
 

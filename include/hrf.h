@@ -424,7 +424,7 @@ HRF_API hrf_status hrf_barcode_counts(const int32_t *bc, int64_t n, int32_t R, i
 HRF_API hrf_status hrf_paint_ids(const int32_t *labels, int64_t n, const int32_t *code, int32_t ncell, int32_t *out,
                                  hrf_stream_t stream);
 
-/* ==== a19: segmented-cosine classification (classify.hip) ===============================
+/* ==== a19: segmented-cosine classification (classify*.hip) ==============================
  * train_reference.py:223-386 (channel_cosine_intensity), :993-1072 (_7b_v2).
  * bounds_host: nseg+1 channel offsets on the HOST (e.g. 0,32,55,75,89,95). */
 /* mode 0: f32 MFMA (v_mfma_f32_32x32x2_f32); mode 1: split-fp16 MFMA (hi/lo' fp16 operands,
