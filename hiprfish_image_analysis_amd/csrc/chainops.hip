@@ -2,7 +2,7 @@
 // ZeroPub).  A hipMemsetAsync or a small hipMemcpyAsync to pinned memory is a rocclr fill or copy
 // kernel of its own; the chains instead fold them into one launch at the points where they
 // synchronise anyway (component boxes, watershed batches, erosion seeding).
-#include "common.hpp"
+#include "devmem.hpp"
 
 namespace {
 
@@ -69,4 +69,8 @@ hipError_t host_alloc_mapped(void **p, size_t bytes) {
   return hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
 }
 
+std::atomic<int64_t> g_live_allocations{0};
+
 }  // namespace hrf
+
+extern "C" int64_t hrf_live_allocations(void) { return hrf::g_live_allocations.load(); }

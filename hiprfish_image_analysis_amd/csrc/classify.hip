@@ -30,6 +30,7 @@
 //         classify_cells.hip   the per-cell path with its entry points
 //         classify.hip         the per-pixel entry points: argument checks and calls into the above
 #include "classify_types.hpp"
+#include "devmem.hpp"
 
 using namespace hrf_cls;
 
@@ -150,19 +151,18 @@ hrf_status hrf_classify_pixels(const float *stack, int64_t P, int32_t C, const v
   if (hrf_status s = resolve(C, bounds_host, nseg, R, mode, &g)) return s;
   hipStream_t s = (hipStream_t)stream;
   const int64_t wb = hrf_classify_refine_work_bytes(P);
-  char *ws = nullptr;
-  HRF_HIP(hipMallocAsync((void **)&ws, (size_t)(al256(4 * P) + wb), s));
-  float *second = (float *)ws;
-  hrf_status st = screen_stack(stack, P, C, refx, R, g, mode, best_idx, best_dist, second, s);
-  if (!st) {
-    const float *src[1] = {stack};
-    const int32_t ch[1] = {C};
-    PixSrc S;
-    st = pixsrc_of(src, ch, nullptr, 1, 1, P, 0, C, &S);
-    if (!st) st = refine(S, P, C, refx, R, g.bd, mode, second, best_idx, best_dist, ws + al256(4 * P), wb, s);
-  }
-  HRF_HIP(hipFreeAsync(ws, s));
-  return st;
+  hrf::StreamBuf<char> ws;
+  HRF_HIP(ws.alloc((size_t)(al256(4 * P) + wb), s));
+  char *base = ws;
+  float *second = (float *)base;
+  HRF_TRY(screen_stack(stack, P, C, refx, R, g, mode, best_idx, best_dist, second, s));
+  const float *src[1] = {stack};
+  const int32_t ch[1] = {C};
+  PixSrc S;
+  HRF_TRY(pixsrc_of(src, ch, nullptr, 1, 1, P, 0, C, &S));
+  HRF_TRY(refine(S, P, C, refx, R, g.bd, mode, second, best_idx, best_dist, base + al256(4 * P), wb, s));
+  HRF_HIP(ws.free());
+  return HRF_OK;
 }
 
 int64_t hrf_pixtable_bytes(int64_t P, int32_t C, const int32_t *bounds_host, int32_t nseg) {

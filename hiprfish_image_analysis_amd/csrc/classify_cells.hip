@@ -1,6 +1,7 @@
 // classify_cells.hip -- the per-cell classifier (reference semantics, gated by presence flags): f64,
 // exact channel order of the restatement -- bit-identical to oracle_segcos.
 #include "classify_types.hpp"
+#include "devmem.hpp"
 
 using namespace hrf_cls;
 
@@ -250,15 +251,15 @@ hrf_status hrf_classify_cells(const double *x, int64_t N, const double *ref, int
   if (N == 0) return HRF_OK;
   HRF_REQUIRE(x && ref && arg && dmin, "classify_cells: null buffer");
   hipStream_t s = (hipStream_t)stream;
-  double *refT = nullptr;
-  HRF_HIP(hipMallocAsync((void **)&refT, sizeof(double) * (size_t)R * (C + bd.nseg), s));
+  hrf::StreamBuf<double> refT;
+  HRF_HIP(refT.alloc((size_t)R * (C + bd.nseg), s));
   double *ny = refT + (size_t)R * C;
   cells_lib_prep_kernel<<<hrf::stream_grid((int64_t)R * C), 256, 0, s>>>(ref, R, C, bd, refT, ny);
   classify_cells_blk_kernel<CELLS_CB, CELLS_NT><<<(unsigned)hrf::cdiv(N, CELLS_CB), CELLS_NT,
                                                   sizeof(double) * CELLS_CB * C, s>>>(
       x, N, refT, ny, R, C, bd, variant, fx, fr, arg, dmin, nullptr);
   HRF_LAUNCHED();
-  HRF_HIP(hipFreeAsync(refT, s));
+  HRF_HIP(refT.free());
   return HRF_OK;
 }
 

@@ -39,6 +39,11 @@ struct Err {
     }                                                                               \
   } while (0)
 
+#define HRF_TRY(expr)                      \
+  do {                                     \
+    if (hrf_status r_ = (expr)) return r_; \
+  } while (0)
+
 #define HRF_LAUNCHED()                                                              \
   do {                                                                              \
     hipError_t e_ = hipGetLastError();                                              \

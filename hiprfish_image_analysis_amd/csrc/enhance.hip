@@ -13,12 +13,10 @@
 // 8-accumulator pairwise mean, numpy percentile lerp), compiled with -ffp-contract=off, so
 // results are bit-identical to the reference chain.
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <tuple>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "lp_tables.inc"
 
 namespace {
@@ -311,31 +309,18 @@ __global__ void lp3d_norm_generic_kernel(const double *__restrict__ pad, int64_t
 }
 
 // Device copies of runtime tables, uploaded once per parameter set.
-std::mutex g_tab_mu;
-std::map<std::tuple<int, int, int, int, int>, int32_t *> g_tabs;
+hrf::DeviceTables<std::tuple<int, int, int, int>, int32_t> g_tabs;
 
-hrf_status device_table(int dims, int patch, int ntheta, int nphi, int32_t **out) {
-  int dev = 0;
-  HRF_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_tab_mu);
-  auto key = std::make_tuple(dev, dims, patch, ntheta, nphi);
-  auto it = g_tabs.find(key);
-  if (it != g_tabs.end()) {
-    *out = it->second;
-    return HRF_OK;
-  }
-  const int ndir = dims == 2 ? nphi : (ntheta - 1) * nphi;
-  std::vector<int32_t> h((size_t)ndir * patch * dims);
-  if (dims == 2)
-    hrf::lp_table_2d(patch, nphi, h.data());
-  else
-    hrf::lp_table_3d(patch, ntheta, nphi, h.data());
-  int32_t *d = nullptr;
-  HRF_HIP(hipMalloc(&d, h.size() * sizeof(int32_t)));
-  HRF_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  g_tabs[key] = d;
-  *out = d;
-  return HRF_OK;
+hrf_status device_table(int dims, int patch, int ntheta, int nphi, const int32_t **out) {
+  auto build = [=](std::vector<int32_t> &h) {
+    const int ndir = dims == 2 ? nphi : (ntheta - 1) * nphi;
+    h.resize((size_t)ndir * patch * dims);
+    if (dims == 2)
+      hrf::lp_table_2d(patch, nphi, h.data());
+    else
+      hrf::lp_table_3d(patch, ntheta, nphi, h.data());
+  };
+  return g_tabs.get(std::make_tuple(dims, patch, ntheta, nphi), build, out);
 }
 
 }  // namespace
@@ -349,7 +334,7 @@ hrf_status hrf_line_profile_2d(const double *pad, int64_t hp, int64_t wp, int64_
   const int64_t H = hp - (patch - 1), W = wp - (patch - 1);
   if (H == 0 || W == 0) return HRF_OK;
   HRF_REQUIRE(pad && out, "line_profile_2d: null buffer");
-  int32_t *tab = nullptr;
+  const int32_t *tab = nullptr;
   hrf_status s = device_table(2, patch, 0, nphi, &tab);
   if (s) return s;
   const int64_t n = H * W * nphi * patch;
@@ -380,7 +365,7 @@ hrf_status hrf_line_profile_3d(const double *pad, int64_t xp, int64_t yp, int64_
   const int64_t X = xp - (patch - 1), Y = yp - (patch - 1), Z = zp - (patch - 1);
   if (X == 0 || Y == 0 || Z == 0) return HRF_OK;
   HRF_REQUIRE(pad && out, "line_profile_3d: null buffer");
-  int32_t *tab = nullptr;
+  const int32_t *tab = nullptr;
   hrf_status s = device_table(3, patch, ntheta, nphi, &tab);
   if (s) return s;
   const int ndir = (ntheta - 1) * nphi;
@@ -407,7 +392,7 @@ hrf_status hrf_line_profile_3d_norm(const double *pad, int64_t xp, int64_t yp, i
     HRF_LAUNCHED();
     return HRF_OK;
   }
-  int32_t *tab = nullptr;
+  const int32_t *tab = nullptr;
   hrf_status s = device_table(3, patch, ntheta, nphi, &tab);
   if (s) return s;
   const int ndir = (ntheta - 1) * nphi;

@@ -1812,6 +1812,7 @@ hrf_status hrf_kmeans_1d_sorted(const double *x, const uint8_t *valid, int64_t n
   const SortWs ws = carve(work, n, tb);
   hipStream_t s = (hipStream_t)stream;
   KmState *&fin = last_single_state();
+  // one pinned slot per host thread, process-lifetime by design
   if (!fin) HRF_HIP(hipHostMalloc((void **)&fin, sizeof(KmState), hipHostMallocDefault));
   if (hrf_status r = km_launch_k(k, x, valid, n, max_iter, n_init, top_rule, labels, top_mask, ws, reuse_sort, s, fin))
     return r;
@@ -1872,6 +1873,7 @@ hrf_status hrf_kmeans_1d_sorted_pair(const double *x, const uint8_t *valid, int6
   hipStream_t s = (hipStream_t)stream;
   // both fits enqueued (the second reuses the sort), one synchronisation for the NaN check
   static thread_local KmState *fin = nullptr;
+  // one pinned slot per host thread, process-lifetime by design
   if (!fin) HRF_HIP(hipHostMalloc((void **)&fin, sizeof(KmState), hipHostMallocDefault));
   if (hrf_status r = km_launch_k(k1, x, valid, n, max_iter, n_init, rule1, nullptr, top1, ws, 0, s, nullptr)) return r;
   if (hrf_status r = km_launch_k(k2, x, valid, n, max_iter, n_init, rule2, nullptr, top2, ws, 1, s, fin)) return r;

@@ -23,7 +23,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "wave.hpp"
 
 namespace {
@@ -570,6 +570,7 @@ struct PxScratchLease {
         return hipSuccess;
       }
     }
+    // process-lifetime by design: the pool keeps it, nothing releases it
     return hipMalloc((void **)&buf, (size_t)::hrf::seed_px_scratch_bytes());
   }
   ~PxScratchLease() {
@@ -616,8 +617,8 @@ hrf_status hrf_erosion_seeds(const int32_t *labels, int64_t H, int64_t W, int32_
   PxScratchLease pxl(dev, s);
   HRF_HIP(pxl.acquire());
   char *pxs = pxl.buf;
-  int32_t *ovf = nullptr;
-  HRF_HIP(hipMallocAsync((void **)&ovf, sizeof(int32_t), s));
+  hrf::StreamBuf<int32_t> ovf;
+  HRF_HIP(ovf.alloc(1, s));
   hrf_status st =
       ::hrf::erosion_seeds_hostbox(labels, H, W, ncomp, box, hb.data(), area_max, min_obj, be_out, s, ovf, pxs);
   int32_t novf = 0;
@@ -625,7 +626,7 @@ hrf_status hrf_erosion_seeds(const int32_t *labels, int64_t H, int64_t W, int32_
     HRF_HIP(hipMemcpyAsync(&novf, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HRF_HIP(hipStreamSynchronize(s));
   }
-  HRF_HIP(hipFreeAsync(ovf, s));
+  HRF_HIP(ovf.free());
   // a large-box component overflowed the run kernel: redo the classic way
   if (st == HRF_OK && novf > 0) {
     st = ::hrf::erosion_seeds_hostbox(labels, H, W, ncomp, box, hb.data(), area_max, min_obj, be_out, s, nullptr,
@@ -666,14 +667,16 @@ hrf_status hrf::erosion_seeds_hostbox(const int32_t *labels, int64_t H, int64_t 
   }
   // the run kernel lists, on the device, the components it hands to the pixel kernel (nothing
   // is copied from host memory, whose lifetime an asynchronous copy would outlive)
-  int32_t *dlist = nullptr;
+  StreamBuf<char> dlist_mem;
   const size_t nl = (size_t)ncomp + 3;
   const int npx_wg = std::min(ncomp, SEED_PX_WG);
   const size_t list_bytes = (sizeof(int32_t) * nl + 255) & ~(size_t)255;
   // the pixel kernel's scratch: the caller's (the native driver's context holds one), else
   // allocated with the list
-  HRF_HIP(hipMallocAsync((void **)&dlist, list_bytes + (px_scratch ? 0 : (size_t)npx_wg * SEED_SLICE), s));
-  if (!px_scratch) px_scratch = reinterpret_cast<char *>(dlist) + list_bytes;
+  HRF_HIP(dlist_mem.alloc(list_bytes + (px_scratch ? 0 : (size_t)npx_wg * SEED_SLICE), s));
+  char *base = dlist_mem;
+  int32_t *dlist = reinterpret_cast<int32_t *>(base);
+  if (!px_scratch) px_scratch = base + list_bytes;
   int32_t *dcount = dlist + ncomp + 1;  // [0] pixel-kernel list length, [1] large-box overflows
   // the seed image, the counters and the caller's overflow slot cleared by one launch
   ZeroPub zp;
@@ -696,12 +699,13 @@ hrf_status hrf::erosion_seeds_hostbox(const int32_t *labels, int64_t H, int64_t 
     const int64_t r0 = br0 > 0 ? br0 - 1 : 0, c0 = bc0 > 0 ? bc0 - 1 : 0;
     const int64_t r1 = br1 < H - 1 ? br1 + 1 : H - 1, c1 = bc1 < W - 1 ? bc1 + 1 : W - 1;
     const int64_t h = r1 - r0 + 1, w = c1 - c0 + 1, n = h * w;
-    char *ws = nullptr;
-    HRF_HIP(hipMallocAsync((void **)&ws, (size_t)(3 * n + 8 * n + 64), s));
+    StreamBuf<char> ws_mem;
+    HRF_HIP(ws_mem.alloc((size_t)(3 * n + 8 * n + 64), s));
+    char *ws = ws_mem;
     uint8_t *m = (uint8_t *)ws, *m2 = m + n, *bec = m2 + n;
     int32_t *par = (int32_t *)(ws + ((3 * n + 15) & ~(int64_t)15)), *sz = par + n;
-    int64_t *cnt_dev = nullptr;
-    HRF_HIP(hipMallocAsync((void **)&cnt_dev, sizeof(int64_t), s));
+    StreamBuf<int64_t> cnt_dev;
+    HRF_HIP(cnt_dev.alloc(1, s));
     HRF_HIP(hipMemsetAsync(bec, 0, (size_t)n, s));
     big_crop_kernel<<<hrf::stream_grid(n), 256, 0, s>>>(labels, H, W, box, ncomp, mode, r0, c0, h, w, m);
     HRF_LAUNCHED();
@@ -720,9 +724,9 @@ hrf_status hrf::erosion_seeds_hostbox(const int32_t *labels, int64_t H, int64_t 
       big_paste_kernel<<<hrf::stream_grid(n), 256, 0, s>>>(bec, H, W, r0, c0, h, w, be_out);
       HRF_LAUNCHED();
     }
-    HRF_HIP(hipFreeAsync(cnt_dev, s));
-    HRF_HIP(hipFreeAsync(ws, s));
+    HRF_HIP(cnt_dev.free());
+    HRF_HIP(ws_mem.free());
   }
-  HRF_HIP(hipFreeAsync(dlist, s));
+  HRF_HIP(dlist_mem.free());
   return st;
 }

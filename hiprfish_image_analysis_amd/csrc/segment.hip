@@ -10,75 +10,70 @@
 // pipeline.py, step for step; tests check the two give identical label maps.
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
-#include "common.hpp"
+#include "devmem.hpp"
+
+using hrf::DevBuf;
+using hrf::PinnedBuf;
 
 struct hrf_seg_ctx {
   int64_t H = 0, W = 0, n = 0;
   int device = 0;
   // f64 images
-  double *cn = nullptr, *f1 = nullptr, *f2 = nullptr, *f3 = nullptr, *pad = nullptr;
-  double *scal = nullptr;  // device scalar (max)
+  DevBuf<double> cn, f1, f2, f3, pad;
+  DevBuf<double> scal;  // device scalar (max)
   // u8 masks
-  uint8_t *m[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf<uint8_t> m[6];
   // int32 images / scratch
-  int32_t *l[4] = {nullptr, nullptr, nullptr, nullptr};
-  int32_t *parent = nullptr, *size = nullptr, *blk = nullptr, *dint = nullptr;
-  void *ws_state = nullptr;
-  int32_t *ws_flag = nullptr;
-  int32_t *hpin = nullptr;  // pinned host slots for counts read back at a later synchronisation
-  int32_t *hpin_dev = nullptr, *hbox_dev = nullptr;  // their device addresses (hrf::zero_publish)
-  void *km = nullptr;
+  DevBuf<int32_t> l[4];
+  DevBuf<int32_t> parent, size, blk, dint;
+  DevBuf<char> ws_state;
+  DevBuf<int32_t> ws_flag;
+  // pinned host slots for counts read back at a later synchronisation (.dev(): hrf::zero_publish)
+  PinnedBuf hpin;
+  DevBuf<char> km;
   int64_t km_bytes = 0;
-  char *seed_px = nullptr;  // erosion seeding's pixel-kernel scratch
+  DevBuf<char> seed_px;  // erosion seeding's pixel-kernel scratch
   // the last chain's watershed: passes, contested pixels, resolution rounds, decisions between
   // equal-valued markers of different labels (hrf_watershed_ex ties_host) -- hrf_seg_ctx_stats
   int32_t ws_stats[4] = {0, 0, 0, 0};
   // per-label scratch, grown on demand
   int64_t lab_cap = 0;
-  int32_t *box = nullptr, *cnt = nullptr;
-  int32_t *hbox = nullptr;  // pinned host copy of box (4 * lab_cap)
-  int64_t *mom = nullptr;
-  double *props = nullptr;
+  DevBuf<int32_t> box, cnt;
+  PinnedBuf hbox;  // pinned host copy of box (4 * lab_cap)
+  DevBuf<int64_t> mom;
+  DevBuf<double> props;
 };
 
 namespace {
 
-template <class T>
-hrf_status dalloc(T **p, size_t count) {
-  HRF_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
-  return HRF_OK;
-}
-
+// Grows the per-label buffers to hold labels 0..maxlab.  The larger set is allocated first and
+// moved in (releasing the old one) only when all of it exists; on failure c is unchanged.
 hrf_status ensure_labels(hrf_seg_ctx *c, int64_t maxlab, hipStream_t s) {
   if (maxlab + 1 <= c->lab_cap) return HRF_OK;
   HRF_HIP(hipStreamSynchronize(s));  // buffers of the previous size may still be in use
-  hipFree(c->box);
-  hipFree(c->cnt);
-  hipFree(c->mom);
-  hipFree(c->props);
-  if (c->hbox) hipHostFree(c->hbox);
-  c->hbox = nullptr;
-  c->hbox_dev = nullptr;
   int64_t cap = 1024;
   while (cap < maxlab + 1) cap *= 2;
-  if (hrf_status r = dalloc(&c->box, 4 * cap)) return r;
-  if (hrf_status r = dalloc(&c->cnt, cap)) return r;
-  if (hrf_status r = dalloc(&c->mom, 6 * cap)) return r;
-  if (hrf_status r = dalloc(&c->props, 8 * cap)) return r;
-  if (::hrf::host_alloc_mapped((void **)&c->hbox, sizeof(int32_t) * 4 * cap) != hipSuccess ||
-      !(c->hbox_dev = ::hrf::mapped(c->hbox))) {
-    if (c->hbox) hipHostFree(c->hbox);
-    c->hbox = nullptr;
-    c->lab_cap = 0;
-    ::hrf::set_error("seg_ctx: pinned host allocation failed");
-    return HRF_EHIP;
-  }
+  DevBuf<int32_t> box, cnt;
+  DevBuf<int64_t> mom;
+  DevBuf<double> props;
+  PinnedBuf hbox;
+  HRF_TRY(box.alloc(4 * cap));
+  HRF_TRY(cnt.alloc(cap));
+  HRF_TRY(mom.alloc(6 * cap));
+  HRF_TRY(props.alloc(8 * cap));
+  HRF_TRY(hbox.alloc(4 * cap, "seg_ctx"));
   // the chain clears cnt and mom at the watershed's synchronisation (capacity-wide); buffers
   // allocated after it are cleared here
-  HRF_HIP(hipMemsetAsync(c->cnt, 0, sizeof(int32_t) * cap, s));
-  HRF_HIP(hipMemsetAsync(c->mom, 0, sizeof(int64_t) * 6 * cap, s));
+  HRF_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * cap, s));
+  HRF_HIP(hipMemsetAsync(mom, 0, sizeof(int64_t) * 6 * cap, s));
+  c->box = std::move(box);
+  c->cnt = std::move(cnt);
+  c->mom = std::move(mom);
+  c->props = std::move(props);
+  c->hbox = std::move(hbox);
   c->lab_cap = cap;
   return HRF_OK;
 }
@@ -88,11 +83,6 @@ hrf_status read_i32(const int32_t *dev, int32_t *host, hipStream_t s) {
   HRF_HIP(hipStreamSynchronize(s));
   return HRF_OK;
 }
-
-#define HRF_TRY(expr)                   \
-  do {                                  \
-    if (hrf_status r_ = (expr)) return r_; \
-  } while (0)
 
 // skimage.measure.label(mask, connectivity=2) -> labels, count (host)
 hrf_status label_conn2(hrf_seg_ctx *c, const uint8_t *mask, int32_t *labels, int32_t *nlab, hipStream_t s) {
@@ -120,66 +110,36 @@ extern "C" {
 
 hrf_status hrf_seg_ctx_create(int64_t H, int64_t W, hrf_seg_ctx **out) {
   HRF_REQUIRE(out && H >= 1 && W >= 1 && H * W < ((int64_t)1 << 31), "seg_ctx: bad size");
-  hrf_seg_ctx *c = new hrf_seg_ctx();
+  auto c = std::make_unique<hrf_seg_ctx>();
   c->H = H;
   c->W = W;
   c->n = H * W;
   const size_t n = (size_t)c->n;
-  hrf_status r = HRF_OK;
-  auto fail = [&](hrf_status st) {
-    hrf_seg_ctx_destroy(c);
-    return st;
-  };
   HRF_HIP(hipGetDevice(&c->device));
-  if ((r = dalloc(&c->cn, n)) || (r = dalloc(&c->f1, n)) || (r = dalloc(&c->f2, n)) || (r = dalloc(&c->f3, n)) ||
-      (r = dalloc(&c->pad, (size_t)(H + 10) * (W + 10))) || (r = dalloc(&c->scal, 8)))
-    return fail(r);
-  for (auto &p : c->m)
-    if ((r = dalloc(&p, n))) return fail(r);
-  for (auto &p : c->l)
-    if ((r = dalloc(&p, n))) return fail(r);
-  if ((r = dalloc(&c->parent, n)) || (r = dalloc(&c->size, n)) || (r = dalloc(&c->blk, (size_t)::hrf::label_dev_ws_words(c->n))) ||
-      (r = dalloc(&c->dint, 16)) || (r = dalloc(&c->ws_flag, 8)))
-    return fail(r);
-  if ((r = dalloc((char **)&c->ws_state, (size_t)hrf_watershed_workspace_bytes(H, W)))) return fail(r);
-  if (::hrf::host_alloc_mapped((void **)&c->hpin, 16 * sizeof(int32_t)) != hipSuccess ||
-      !(c->hpin_dev = ::hrf::mapped(c->hpin))) {
-    ::hrf::set_error("seg_ctx: pinned host allocation failed");
-    return fail(HRF_EHIP);
-  }
+  HRF_TRY(c->cn.alloc(n));
+  HRF_TRY(c->f1.alloc(n));
+  HRF_TRY(c->f2.alloc(n));
+  HRF_TRY(c->f3.alloc(n));
+  HRF_TRY(c->pad.alloc((size_t)(H + 10) * (W + 10)));
+  HRF_TRY(c->scal.alloc(8));
+  for (auto &p : c->m) HRF_TRY(p.alloc(n));
+  for (auto &p : c->l) HRF_TRY(p.alloc(n));
+  HRF_TRY(c->parent.alloc(n));
+  HRF_TRY(c->size.alloc(n));
+  HRF_TRY(c->blk.alloc((size_t)::hrf::label_dev_ws_words(c->n)));
+  HRF_TRY(c->dint.alloc(16));
+  HRF_TRY(c->ws_flag.alloc(8));
+  HRF_TRY(c->ws_state.alloc((size_t)hrf_watershed_workspace_bytes(H, W)));
+  HRF_TRY(c->hpin.alloc(16, "seg_ctx"));
   c->km_bytes = hrf_kmeans_sorted_workspace_bytes(c->n);
-  if (c->km_bytes <= 0) return fail(HRF_EHIP);
-  if ((r = dalloc((char **)&c->km, (size_t)c->km_bytes))) return fail(r);
-  if ((r = dalloc(&c->seed_px, (size_t)::hrf::seed_px_scratch_bytes()))) return fail(r);
-
-  *out = c;
+  if (c->km_bytes <= 0) return HRF_EHIP;
+  HRF_TRY(c->km.alloc((size_t)c->km_bytes));
+  HRF_TRY(c->seed_px.alloc((size_t)::hrf::seed_px_scratch_bytes()));
+  *out = c.release();
   return HRF_OK;
 }
 
 hrf_status hrf_seg_ctx_destroy(hrf_seg_ctx *c) {
-  if (!c) return HRF_OK;
-  hipFree(c->cn);
-  hipFree(c->f1);
-  hipFree(c->f2);
-  hipFree(c->f3);
-  hipFree(c->pad);
-  hipFree(c->scal);
-  for (auto p : c->m) hipFree(p);
-  for (auto p : c->l) hipFree(p);
-  hipFree(c->parent);
-  hipFree(c->size);
-  hipFree(c->blk);
-  hipFree(c->dint);
-  hipFree(c->ws_state);
-  hipFree(c->ws_flag);
-  if (c->hpin) hipHostFree(c->hpin);
-  if (c->hbox) hipHostFree(c->hbox);
-  hipFree(c->km);
-  hipFree(c->seed_px);
-  hipFree(c->box);
-  hipFree(c->cnt);
-  hipFree(c->mom);
-  hipFree(c->props);
   delete c;
   return HRF_OK;
 }
@@ -209,8 +169,8 @@ static hrf_status segment_ecoli_from_cn(hrf_seg_ctx *c, const double *cn, int32_
   HRF_TRY(hrf_label_boxes(lab1, H, W, guess, c->box, s));
   {
     ::hrf::ZeroPub zp;
-    HRF_REQUIRE(zp.pub(c->dint, c->hpin_dev + 1, 1) && zp.pub(km_err, c->hpin_dev + 3, 1) &&
-                    zp.pub(c->box, c->hbox_dev, 4 * (guess + 1)),
+    HRF_REQUIRE(zp.pub(c->dint, c->hpin.dev() + 1, 1) && zp.pub(km_err, c->hpin.dev() + 3, 1) &&
+                    zp.pub(c->box, c->hbox.dev(), 4 * (guess + 1)),
                 "segment_ecoli: too many read-backs");
     HRF_TRY(::hrf::zero_publish(zp, s));
   }
@@ -222,7 +182,7 @@ static hrf_status segment_ecoli_from_cn(hrf_seg_ctx *c, const double *cn, int32_
     HRF_TRY(ensure_labels(c, ncomp, s));
     HRF_TRY(hrf_label_boxes(lab1, H, W, ncomp, c->box, s));
     ::hrf::ZeroPub zp;
-    HRF_REQUIRE(zp.pub(c->box, c->hbox_dev, 4 * (ncomp + 1)), "segment_ecoli: too many read-backs");
+    HRF_REQUIRE(zp.pub(c->box, c->hbox.dev(), 4 * (ncomp + 1)), "segment_ecoli: too many read-backs");
     HRF_TRY(::hrf::zero_publish(zp, s));
     HRF_HIP(hipStreamSynchronize(s));
   }
@@ -237,7 +197,7 @@ static hrf_status segment_ecoli_from_cn(hrf_seg_ctx *c, const double *cn, int32_
     // read back at the watershed's synchronisation: the seed count, the run kernel's overflow
     // count; cleared there: the per-label counts and moments (capacity-wide) and `extra`
     ::hrf::ZeroPub zp = extra ? *extra : ::hrf::ZeroPub();
-    HRF_REQUIRE(zp.pub(c->dint, c->hpin_dev + 0, 1) && (attempt > 0 || zp.pub(c->dint + 8, c->hpin_dev + 2, 1)) &&
+    HRF_REQUIRE(zp.pub(c->dint, c->hpin.dev() + 0, 1) && (attempt > 0 || zp.pub(c->dint + 8, c->hpin.dev() + 2, 1)) &&
                     zp.zero(c->cnt, sizeof(int32_t) * c->lab_cap) && zp.zero(c->mom, sizeof(int64_t) * 6 * c->lab_cap),
                 "segment_ecoli: too many read-backs");
     HRF_TRY(::hrf::watershed_ex_extra(cn, 1, seeds, rough, H, W, ws, c->ws_state, c->ws_flag, 100000, c->ws_stats,

@@ -16,8 +16,11 @@
 // The calls are the library's own entry points (or their device-count twins), in pipeline.py's
 // order, so the results equal the composed path bit for bit (tests/test_tile_gpu.py).
 #include <algorithm>
+#include <memory>
 
-#include "common.hpp"
+#include "devmem.hpp"
+
+using hrf::DevBuf;
 
 namespace {
 
@@ -27,68 +30,61 @@ constexpr int32_t BOUNDS[NL + 1] = {0, 32, 55, 75, 89, 95};
 constexpr int32_t C = 95;
 constexpr int32_t TILE_CHANMAX_WG = 512;  // the projections' workgroup budget in the tile path
 
-template <class T>
-hrf_status dalloc(T **p, size_t count) {
-  HRF_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
-  return HRF_OK;
-}
-
-#define HRF_TRY(expr)                      \
-  do {                                     \
-    if (hrf_status r_ = (expr)) return r_; \
-  } while (0)
+struct SegCtxDestroy {
+  void operator()(hrf_seg_ctx *c) const { hrf_seg_ctx_destroy(c); }
+};
 
 }  // namespace
 
 struct hrf_tile_ctx {
   int64_t H = 0, W = 0;
-  hrf_seg_ctx *seg = nullptr;
-  double *proj = nullptr;       // NL x H x W channel-max projections
-  void *xwork = nullptr;        // xcorr workspace (power-of-two tiles) or the hipFFT one (others)
+  std::unique_ptr<hrf_seg_ctx, SegCtxDestroy> seg;
+  DevBuf<double> proj;          // NL x H x W channel-max projections
+  DevBuf<char> xwork;           // xcorr workspace (power-of-two tiles) or the hipFFT one (others)
   bool pow2 = true;
-  int32_t *shifts = nullptr;    // NL x 2
-  double *cn = nullptr;         // image_cn
-  void *table = nullptr;        // pixel table
-  uint8_t *flags = nullptr;
-  void *rwork = nullptr;        // the refine's list (hrf_classify_refine_work_bytes)
+  DevBuf<int32_t> shifts;       // NL x 2
+  DevBuf<double> cn;            // image_cn
+  DevBuf<char> table;           // pixel table
+  DevBuf<uint8_t> flags;
+  DevBuf<char> rwork;           // the refine's list (hrf_classify_refine_work_bytes)
   int64_t rwork_bytes = 0;
   bool pix_ran = false;         // the last tile ran the per-pixel classifier (rwork holds its count)
   // per-label buffers, grown on demand (capacity cap labels + 1)
   int64_t cap = 0;
-  double *sums = nullptr;
-  int64_t *counts = nullptr;
-  int32_t *rol = nullptr;
-  double *fx = nullptr;         // cell presence flags (cap x NL)
-  int32_t *nrows = nullptr;     // device row count
-  double *refT = nullptr;       // library, channel-major, then its segment norms (R x 5)
+  DevBuf<double> sums;
+  DevBuf<int64_t> counts;
+  DevBuf<int32_t> rol;
+  DevBuf<double> fx;            // cell presence flags (cap x NL)
+  DevBuf<int32_t> nrows;        // device row count
+  DevBuf<double> refT;          // library, channel-major, then its segment norms (R x 5)
   int64_t refT_cap = 0;
-  hipEvent_t ev_reg = nullptr, ev_pix = nullptr;
+  hrf::Event ev_reg, ev_pix;
   int32_t maxlab = 0;           // the last tile's, for hrf_tile_ecoli_cells
 };
 
 namespace {
 
+// Grows the per-label buffers to hold labels 0..maxlab.  The larger set is allocated first and
+// moved in (releasing the old one) only when all of it exists; on failure t is unchanged.
 hrf_status ensure_cap(hrf_tile_ctx *t, int64_t maxlab, hipStream_t s) {
   if (maxlab + 1 <= t->cap) return HRF_OK;
   HRF_HIP(hipStreamSynchronize(s));  // the previous tile's per-label work is done with them
-  hipFree(t->sums);
-  hipFree(t->counts);
-  hipFree(t->rol);
-  hipFree(t->fx);
-  t->sums = nullptr;
-  t->counts = nullptr;
-  t->rol = nullptr;
-  t->fx = nullptr;
-  t->cap = 0;
   int64_t cap = 2048;
   while (cap < maxlab + 1) cap *= 2;
-  HRF_TRY(dalloc(&t->sums, (size_t)cap * C));
-  HRF_TRY(dalloc(&t->counts, (size_t)cap));
-  HRF_TRY(dalloc(&t->rol, (size_t)cap));
-  HRF_TRY(dalloc(&t->fx, (size_t)cap * NL));
+  DevBuf<double> sums, fx;
+  DevBuf<int64_t> counts;
+  DevBuf<int32_t> rol;
+  HRF_TRY(sums.alloc((size_t)cap * C));
+  HRF_TRY(counts.alloc((size_t)cap));
+  HRF_TRY(rol.alloc((size_t)cap));
+  HRF_TRY(fx.alloc((size_t)cap * NL));
   // later tiles clear sums and counts at the chain's watershed synchronisation
-  HRF_HIP(hipMemsetAsync(t->sums, 0, sizeof(double) * (size_t)cap * C, s));
-  HRF_HIP(hipMemsetAsync(t->counts, 0, sizeof(int64_t) * (size_t)cap, s));
+  HRF_HIP(hipMemsetAsync(sums, 0, sizeof(double) * (size_t)cap * C, s));
+  HRF_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)cap, s));
+  t->sums = std::move(sums);
+  t->counts = std::move(counts);
+  t->rol = std::move(rol);
+  t->fx = std::move(fx);
   t->cap = cap;
   return HRF_OK;
 }
@@ -105,10 +101,9 @@ hrf_status tile_cells(hrf_tile_ctx *t, const int32_t *seg, const double *lib, co
   if (variant) HRF_TRY(hrf::segment_flags_devn(avgint_norm, maxlab, ncells_dev, C, BOUNDS, NL, flag_thr, t->fx, s));
   if ((int64_t)R * (C + NL) > t->refT_cap) {
     HRF_HIP(hipStreamSynchronize(s));
-    hipFree(t->refT);
-    t->refT = nullptr;
-    t->refT_cap = 0;
-    HRF_TRY(dalloc(&t->refT, (size_t)R * (C + NL)));
+    DevBuf<double> refT;
+    HRF_TRY(refT.alloc((size_t)R * (C + NL)));
+    t->refT = std::move(refT);
     t->refT_cap = (int64_t)R * (C + NL);
   }
   double *ny = t->refT + (size_t)R * C;
@@ -136,50 +131,30 @@ hrf_status hrf_tile_ctx_create(int64_t H, int64_t W, hrf_tile_ctx **out) {
   HRF_REQUIRE(xb > 0, "tile_ctx: registration workspace size");
   const int64_t tb = hrf_pixtable_bytes(H * W, C, BOUNDS, NL);
   HRF_REQUIRE(tb > 0, "tile_ctx: pixel table size");
-  hrf_tile_ctx *t = new hrf_tile_ctx();
+  auto t = std::make_unique<hrf_tile_ctx>();
   t->H = H;
   t->W = W;
   t->pow2 = xw > 0;
-  auto fail = [&](hrf_status st) {
-    hrf_tile_ctx_destroy(t);
-    return st;
-  };
   const size_t n = (size_t)(H * W);
-  hrf_status r;
-  if ((r = hrf_seg_ctx_create(H, W, &t->seg))) return fail(r);
-  if ((r = dalloc(&t->proj, NL * n)) || (r = dalloc((char **)&t->xwork, (size_t)xb)) ||
-      (r = dalloc(&t->shifts, 2 * NL)) || (r = dalloc(&t->cn, n)) || (r = dalloc((char **)&t->table, (size_t)tb)) ||
-      (r = dalloc(&t->flags, n)) || (r = dalloc(&t->nrows, 4)) ||
-      (r = dalloc((char **)&t->rwork, (size_t)hrf_classify_refine_work_bytes((int64_t)n))))
-    return fail(r);
+  hrf_seg_ctx *seg = nullptr;
+  HRF_TRY(hrf_seg_ctx_create(H, W, &seg));
+  t->seg.reset(seg);
   t->rwork_bytes = hrf_classify_refine_work_bytes((int64_t)n);
-  if (hipEventCreateWithFlags(&t->ev_reg, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&t->ev_pix, hipEventDisableTiming) != hipSuccess) {
-    ::hrf::set_error("tile_ctx: event creation failed");
-    return fail(HRF_EHIP);
-  }
-  *out = t;
+  HRF_TRY(t->proj.alloc(NL * n));
+  HRF_TRY(t->xwork.alloc((size_t)xb));
+  HRF_TRY(t->shifts.alloc(2 * NL));
+  HRF_TRY(t->cn.alloc(n));
+  HRF_TRY(t->table.alloc((size_t)tb));
+  HRF_TRY(t->flags.alloc(n));
+  HRF_TRY(t->nrows.alloc(4));
+  HRF_TRY(t->rwork.alloc((size_t)t->rwork_bytes));
+  HRF_TRY(t->ev_reg.create());
+  HRF_TRY(t->ev_pix.create());
+  *out = t.release();
   return HRF_OK;
 }
 
 hrf_status hrf_tile_ctx_destroy(hrf_tile_ctx *t) {
-  if (!t) return HRF_OK;
-  if (t->seg) hrf_seg_ctx_destroy(t->seg);
-  hipFree(t->proj);
-  hipFree(t->xwork);
-  hipFree(t->shifts);
-  hipFree(t->cn);
-  hipFree(t->table);
-  hipFree(t->flags);
-  hipFree(t->rwork);
-  hipFree(t->nrows);
-  hipFree(t->sums);
-  hipFree(t->counts);
-  hipFree(t->rol);
-  hipFree(t->fx);
-  hipFree(t->refT);
-  if (t->ev_reg) hipEventDestroy(t->ev_reg);
-  if (t->ev_pix) hipEventDestroy(t->ev_pix);
   delete t;
   return HRF_OK;
 }
@@ -197,7 +172,7 @@ hrf_status hrf_tile_ctx_pixel_listed(hrf_tile_ctx *t, int32_t *n_host) {
 
 hrf_status hrf_tile_ctx_seg(hrf_tile_ctx *t, hrf_seg_ctx **seg) {
   HRF_REQUIRE(t && seg, "tile_ctx_seg: bad arguments");
-  *seg = t->seg;
+  *seg = t->seg.get();
   return HRF_OK;
 }
 
@@ -268,7 +243,7 @@ hrf_status hrf_tile_ecoli(hrf_tile_ctx *t, const float *const *lasers_host, cons
     ::hrf::set_error("tile_ecoli: per-label clears do not fit the read-back launch");
     return HRF_EINVAL;
   }
-  hrf_status st = ::hrf::segment_ecoli_cn_extra(t->seg, t->cn, seg, &maxlab, s, &zp);   // :73-127
+  hrf_status st = ::hrf::segment_ecoli_cn_extra(t->seg.get(), t->cn, seg, &maxlab, s, &zp);   // :73-127
   if (st) {
     join();
     return st;

@@ -35,7 +35,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "devmem.hpp"
 #include "ws_core.hpp"
 #ifdef HRF_WSW_DEBUG
 __device__ int g_wsw_dbg = 0;
@@ -741,35 +741,34 @@ hrf_status heap_flood(const double *image, int32_t negate, const int32_t *marker
   const int64_t n = H * W;
   HRF_REQUIRE(n < ((int64_t)1 << 31) - 2, "watershed heap replay: image too large");
   if (n == 0) return HRF_OK;
-  char *scratch = nullptr;
-  HRF_HIP(hipMallocAsync((void **)&scratch, (size_t)heap_flood_scratch_bytes(n), s));
+  hrf::StreamBuf<char> scratch;
+  HRF_HIP(scratch.alloc((size_t)heap_flood_scratch_bytes(n), s));
   static const bool attr = [] {
     return hipFuncSetAttribute((const void *)ws_heap_flood_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)HEAP_LDS_BYTES) == hipSuccess &&
            hipFuncSetAttribute((const void *)ws_heap_flood_kernel<false>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAP_LDS_BYTES) == hipSuccess;
   }();
-  hrf_status st = HRF_OK;
   if (!attr) {
     ::hrf::set_error("watershed heap replay: cannot reserve %d bytes of LDS", (int)HEAP_LDS_BYTES);
-    st = HRF_EHIP;
-  } else {
-    HeapItem *hp = (HeapItem *)scratch;
-    int32_t *lp = (int32_t *)(scratch + (n + 2) * 16);
-    if (mask)
-      ws_heap_flood_kernel<true><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H, (int32_t)W,
-                                                                 out, hp, lp);
-    else
-      ws_heap_flood_kernel<false><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H,
-                                                                  (int32_t)W, out, hp, lp);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
-      st = HRF_EHIP;
-    }
+    return HRF_EHIP;
   }
-  HRF_HIP(hipFreeAsync(scratch, s));
-  return st;
+  char *base = scratch;
+  HeapItem *hp = (HeapItem *)base;
+  int32_t *lp = (int32_t *)(base + (n + 2) * 16);
+  if (mask)
+    ws_heap_flood_kernel<true><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H, (int32_t)W,
+                                                               out, hp, lp);
+  else
+    ws_heap_flood_kernel<false><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H, (int32_t)W,
+                                                                out, hp, lp);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
+    return HRF_EHIP;
+  }
+  HRF_HIP(scratch.free());
+  return HRF_OK;
 }
 
 int64_t walker_bytes(int32_t cap, int32_t hcap, int32_t gcap) {
@@ -830,7 +829,7 @@ hrf_status hrf::watershed_ex_extra(const double *image, int32_t negate, const in
   if (passes_host) *passes_host = 0;
   if (n == 0) return HRF_OK;
   HRF_REQUIRE(image && markers && out_labels && state_ws && flag_ws, "watershed: null buffer");
-  // the batch flags' pinned host slots (one set per host thread, kept for the process)
+  // the batch flags' pinned host slots (one set per host thread; process-lifetime by design)
   static thread_local int32_t *pin = nullptr;
   if (!pin) HRF_HIP(host_alloc_mapped((void **)&pin, 64));
   int32_t *pin_dev = mapped(pin);
@@ -904,17 +903,10 @@ hrf_status hrf::watershed_ex_extra(const double *image, int32_t negate, const in
   int32_t ncontest = 0;
   if (hrf_status r = run(false, &ncontest)) return r;
   int32_t total = 0, rounds = 0;
-  char *scratch = nullptr;
-  int64_t scratch_bytes = 0;
   // stream-ordered: a tile with contests must not stall the other tiles' streams (hipFree
   // would synchronise the whole device)
-  struct Scratch {
-    char **p;
-    hipStream_t s;
-    ~Scratch() {
-      if (*p) (void)hipFreeAsync(*p, s);
-    }
-  } sguard{&scratch, s};
+  StreamBuf<char> scratch;
+  int64_t scratch_bytes = 0;
   while (ncontest > 0) {
     total += ncontest;
     ++rounds;
@@ -930,11 +922,9 @@ hrf_status hrf::watershed_ex_extra(const double *image, int32_t negate, const in
       const int64_t threads = budget / stride > 0 ? budget / stride : 1;
       const int64_t nth = ntodo < threads ? ntodo : threads;
       if (nth * stride > scratch_bytes) {
-        const hipError_t fe = scratch ? hipFreeAsync(scratch, s) : hipSuccess;
-        scratch = nullptr;  // before the status check: the guard must not free it again
         scratch_bytes = 0;
-        HRF_HIP(fe);
-        HRF_HIP(hipMallocAsync((void **)&scratch, (size_t)(nth * stride), s));
+        HRF_HIP(scratch.free());
+        HRF_HIP(scratch.alloc((size_t)(nth * stride), s));
         scratch_bytes = nth * stride;
       }
       HRF_HIP(hipMemsetAsync(flag_ws + 3, 0, sizeof(int32_t), s));

@@ -23,14 +23,11 @@
 // result and takes |.| with its ~1e-16 imaginary noise; here the inverse is real -- both differ
 // from each other only in rounding, as the hipFFT path did (tests/test_registration_gpu.py).
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <vector>
 
 #include <cstdlib>
 
-#include "common.hpp"
+#include "devmem.hpp"
 
 namespace {
 
@@ -376,31 +373,18 @@ int ilog2(int64_t n) {
 }
 
 // exp(-2 pi i j / N), j < N, per (device, N): uploaded once (synchronously, on first use)
-std::mutex g_tw_mu;
-std::map<std::tuple<int, int64_t>, double2 *> g_tw;
+hrf::DeviceTables<int64_t, double2> g_tw;
 
 hrf_status twiddles(int64_t N, const double2 **out) {
-  int dev = 0;
-  HRF_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_tw_mu);
-  auto key = std::make_tuple(dev, N);
-  auto it = g_tw.find(key);
-  if (it != g_tw.end()) {
-    *out = it->second;
-    return HRF_OK;
-  }
-  std::vector<double2> h((size_t)N);
-  const long double two_pi = 6.283185307179586476925286766559005768L;
-  for (int64_t j = 0; j < N; ++j) {
-    const long double a = two_pi * (long double)j / (long double)N;
-    h[(size_t)j] = make_double2((double)cosl(a), (double)-sinl(a));
-  }
-  double2 *d = nullptr;
-  HRF_HIP(hipMalloc((void **)&d, sizeof(double2) * (size_t)N));
-  HRF_HIP(hipMemcpy(d, h.data(), sizeof(double2) * (size_t)N, hipMemcpyHostToDevice));
-  g_tw[key] = d;
-  *out = d;
-  return HRF_OK;
+  auto build = [N](std::vector<double2> &h) {
+    h.resize((size_t)N);
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    for (int64_t j = 0; j < N; ++j) {
+      const long double a = two_pi * (long double)j / (long double)N;
+      h[(size_t)j] = make_double2((double)cosl(a), (double)-sinl(a));
+    }
+  };
+  return g_tw.get(N, build, out);
 }
 
 bool supported(int32_t nimg, int64_t H, int64_t W) {

@@ -339,6 +339,12 @@ HRF_API hrf_status hrf_seg_ctx_destroy(hrf_seg_ctx *ctx);
 /* the context's last chain, its watershed: out[4] = passes, contested pixels, resolution
  * rounds, equal-valued-marker decisions (hrf_watershed_ex ties_host) */
 HRF_API hrf_status hrf_seg_ctx_stats(const hrf_seg_ctx *ctx, int32_t *out);
+/* diagnostic: device, stream-ordered and pinned buffers and events the library owns right now
+ * (contexts and the temporaries of calls in flight; process-lifetime tables and pools are not
+ * counted).  A call that has returned, with or without an error, has given back its temporaries;
+ * a call on a context may leave the count higher, because the context grows its per-label
+ * buffers and its library copy on demand and keeps them until it is destroyed. */
+HRF_API int64_t hrf_live_allocations(void);
 /* ecoli measurement.py:44-127: seg_out (H*W int32, labels not re-sequenced), *maxlab_host */
 HRF_API hrf_status hrf_segment_ecoli(hrf_seg_ctx *ctx, const float *stack, int32_t C, int32_t *seg_out,
                                      int32_t *maxlab_host, hrf_stream_t stream);

@@ -299,3 +299,143 @@ def test_tile_native_equal_marker_ties(mods, orc):
     assert np.array_equal(nat.cell_idx.cpu().numpy()[:nat.ncells], o["cell_idx"])
     comp = P.process_tile(P.register_tile(lasers), lib, per_pixel=True, variant=1)
     _check(nat, comp)
+
+
+# ---- ownership: hrf_live_allocations() counts what the library's holders own (csrc/devmem.hpp) ----
+def _live():
+    from hiprfish_image_analysis_amd import _lib as native
+    torch.cuda.synchronize()
+    return native.lib().hrf_live_allocations()
+
+
+def test_context_create_destroy_returns_every_allocation():
+    import ctypes
+    from hiprfish_image_analysis_amd import _lib as native
+    before = _live()
+    for create, destroy in (("hrf_seg_ctx_create", "hrf_seg_ctx_destroy"),
+                            ("hrf_tile_ctx_create", "hrf_tile_ctx_destroy")):
+        h = ctypes.c_void_p()
+        native.call(create, 64, 64, ctypes.addressof(h))
+        assert h.value and _live() > before
+        native.call(destroy, h)
+        assert _live() == before
+    h = ctypes.c_void_p()
+    with pytest.raises(ValueError):      # W is not a multiple of 16
+        native.call("hrf_tile_ctx_create", 64, 72, ctypes.addressof(h))
+    assert not h.value and _live() == before
+
+
+def test_entry_points_release_their_temporaries(mods, orc):
+    """one call of every entry point that takes stream-ordered temporaries: its existing test's
+    assertion holds and no allocation outlives the call"""
+    import pipeline as OP
+    from test_kernels_gpu import check_pixel_argmin, dev, host
+    from test_watershed_gpu import _heap_case
+    K, P, S = mods
+    # erosion seeding with a comb above the run kernel's capacity: redone in the whole-image loop
+    # (test_kernels_gpu.test_erosion_seeds_large_boxes)
+    m = np.zeros((420, 440), bool)
+    m[230:400, 200:410:4] = True
+    m[230:233, 200:410] = True
+    m[300:340, 20:60] = True
+    dm = dev(m)
+    before = _live()
+    got = K.erosion_seeds(dm)
+    assert _live() == before
+    assert np.array_equal(host(got).astype(bool), OP.erosion_seeds(m))
+    # a plateau with contests (test_watershed_gpu.test_watershed_constant_image)
+    H, W = 160, 150
+    markers = np.zeros((H, W), np.int32)
+    rng = np.random.default_rng(5)
+    for l in range(1, 9):
+        r, c = rng.integers(0, H - 3), rng.integers(0, W - 3)
+        markers[r:r + 3, c:c + 3] = l
+    f = -1e-3 * markers
+    df, dmk = dev(f), dev(markers)
+    ties = []
+    before = _live()
+    got = K.watershed(df, dmk, None, ties=ties)
+    assert _live() == before
+    assert ties[0] > 0 and ties[2] == 0
+    assert np.array_equal(host(got), orc.watershed(f, markers, None))
+    # the heap replay alone (test_watershed_gpu.test_watershed_heap_replay_equals_oracle, seed 2)
+    f, markers, mask = _heap_case(2, 45, 61)
+    df, dmk = dev(f), dev(markers)
+    before = _live()
+    got = K.watershed_heap(df, dmk, None)
+    assert _live() == before
+    assert mask is None and np.array_equal(host(got), orc.watershed(f, markers, None))
+    # per-pixel classification of a stack (test_classify_exact_gpu.test_small_and_ragged_pixel_counts)
+    bounds = S.ECOLI_BOUNDS
+    ref = S.reference_library(10, bounds).astype(np.float32)
+    R, C = ref.shape
+    rng = np.random.default_rng(300)
+    x = ref[rng.integers(0, R, 300)] * rng.uniform(0.5, 1, (300, 1)) + rng.normal(0, 0.02, (300, C))
+    x = np.clip(x, 0, None).astype(np.float32)
+    st = dev(x.reshape(1, 300, C))
+    refx = K.classify_prepare(dev(ref), bounds, mode=2)
+    before = _live()
+    gi, gd = K.classify_pixels(st, refx, R, bounds)
+    assert _live() == before
+    check_pixel_argmin(orc, host(gi).ravel(), host(gd).ravel(), x.astype(np.float64), ref.astype(np.float64), bounds)
+    # per-cell classification, gated variant (test_kernels_gpu, the classify_cells variants)
+    ref = ref.astype(np.float64)
+    rng = np.random.default_rng(1)
+    x = ref[rng.integers(0, R, 300)] * rng.uniform(0.5, 1, (300, 1)) + rng.normal(0, 0.05, (300, 95))
+    x = np.clip(x, 0, None)
+    x /= x.max(axis=1, keepdims=True)
+    fr = np.stack([(ref[:, bounds[k]:bounds[k + 1]].max(axis=1) > 0.1) for k in range(5)], 1).astype(np.float64)
+    fx = np.stack([(x[:, bounds[k]:bounds[k + 1]].max(axis=1) > 0.1) for k in range(5)], 1).astype(np.float64)
+    dx, dref, dfx, dfr = dev(x), dev(ref), dev(fx), dev(fr)
+    before = _live()
+    a, d = K.classify_cells(dx, dref, bounds, 1, dfx, dfr)
+    assert _live() == before
+    ra, rd = orc.classify(x, ref, bounds, 1, fx, fr)
+    assert np.array_equal(host(a), ra) and np.array_equal(host(d), rd)
+
+
+def test_label_buffers_grow_past_both_capacities(mods):
+    """a field of 44 x 51 = 2244 bright 8 x 8 blobs at pitch 10 above a row of twelve discs of
+    diameter 24: oracle/pipeline.py's restatement labels 2256 seeds on it (pitch 11 leaves no room
+    for the discs).  No blob's basin reaches the chain's 100-pixel floor, so the surviving cells are
+    the twelve discs, labels 2245..2256 -- every one of them beyond both starting capacities, so
+    their boxes, counts, moments, sums and flags live in the grown part of the buffers.  After an
+    ordinary tile on contexts of the same size the segmentation context's per-label buffers grow
+    past 1024 labels and the tile context's past 2048, and both chains still equal the composed
+    path; releasing the contexts returns every allocation"""
+    K, P, S = mods
+    H = W = 512
+    K.release_contexts()
+    before = _live()
+    lib = _lib(P, S)
+    field = torch.full((H, W), 20.0, dtype=torch.float64)
+    for i in range(44):
+        for j in range(51):
+            field[10 * i:10 * i + 8, 10 * j:10 * j + 8] = 2000.0
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    for cx in range(30, W - 30, 40):
+        field[(yy - 476) ** 2 + (xx - cx) ** 2 <= 144] = 2000.0
+    field = field.cuda()
+    small = _lasers(S, H, W, 20190115)
+    # the segmentation chain alone, from image_cn
+    K.segment_ecoli_native(None, image_cn=P.register_tile(small).image_cn)
+    cn = torch.log(field + 1e-2)
+    seg_n, mx_n = K.segment_ecoli_native(None, image_cn=cn)
+    seg_c, mx_c = P.segment_ecoli(None, keep={}, image_cn=cn)       # composed from Python
+    assert mx_n == mx_c and mx_n > 2048
+    kept = torch.unique(seg_n[seg_n > 0])
+    assert kept.numel() >= 10 and int(kept.min()) > 2048
+    assert _same(seg_n, seg_c)
+    # the same field as five lasers through the native tile
+    spectrum = torch.from_numpy(S.reference_library(10, S.ECOLI_BOUNDS)[3].astype(np.float32)).cuda()
+    lasers = S.laser_split((field.float()[:, :, None] * spectrum[None, None, :]).contiguous(), shifts=[(0, 0)] * 5)
+    first = P.process_tile_native(small, lib, variant=1)
+    assert 0 < first.meas.maxlab < 1024
+    nat = P.process_tile_native(lasers, lib, variant=1)
+    ref = P.process_tile(P.register_tile(lasers), lib, per_pixel=True, variant=1)
+    torch.cuda.synchronize()
+    assert nat.meas.maxlab > 2048
+    assert nat.ncells >= 10 and int(nat.meas.labels[:nat.ncells].min()) > 2048
+    _check(nat, ref)
+    K.release_contexts()
+    assert _live() == before
