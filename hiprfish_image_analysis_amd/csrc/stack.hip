@@ -403,7 +403,11 @@ void launch_assemble(const Lasers &L, int64_t H, int64_t W, int apply_mask, floa
     launch_assemble_b<false>(L, H, W, apply_mask, dst, cn_out, cn_mode, table, flags, s);
 }
 
-// numpy pairwise_sum over n f32 values (as f64), n <= 512
+// numpy pairwise_sum over n f32 values (as f64), n <= 512: blocks of at most 128 values in eight
+// accumulators; a longer run is halved (the first half rounded down to a multiple of 8) until
+// every piece is a block.  The larger piece of n values holds at most n / 2 + 8, so 512 -> 264 ->
+// 140 -> 78: three levels of halving reach a block from any n <= 512, unrolled at compile time
+// (no recursion, no scratch stack).
 __device__ double pw_block(const float *a, int n) {
   if (n < 8) {
     double res = 0.0;
@@ -421,18 +425,18 @@ __device__ double pw_block(const float *a, int n) {
   for (; i < n; ++i) res += (double)a[i];
   return res;
 }
-__device__ double pw_l1(const float *a, int n) {
-  if (n <= 128) return pw_block(a, n);
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pw_block(a, n2) + pw_block(a + n2, n - n2);
+template <int LEVELS>
+__device__ double pw_split(const float *a, int n) {
+  if constexpr (LEVELS == 0) {
+    return pw_block(a, n);
+  } else {
+    if (n <= 128) return pw_block(a, n);
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return pw_split<LEVELS - 1>(a, n2) + pw_split<LEVELS - 1>(a + n2, n - n2);
+  }
 }
-__device__ double pw_sum(const float *a, int n) {
-  if (n <= 256) return pw_l1(a, n);
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return pw_l1(a, n2) + pw_l1(a + n2, n - n2);
-}
+__device__ double pw_sum(const float *a, int n) { return pw_split<3>(a, n); }
 
 __global__ void channel_sum_kernel(const float *__restrict__ stack, int64_t npix, int C,
                                    const uint8_t *__restrict__ mask, int mode, int negate, double *__restrict__ out) {
@@ -555,11 +559,14 @@ __global__ __launch_bounds__(256) void channel_sum_lds_kernel(const float *__res
 #undef CS_PUT
 
 __global__ void max_f64_kernel(const double *__restrict__ a, int64_t n, unsigned long long *__restrict__ mx) {
-  // order-preserving encoding so atomicMax on uint64 is a max on doubles
+  // order-preserving encoding so atomicMax on uint64 is a max on doubles (0 is the code of no
+  // number: -NaN with a full mantissa would map there, and every NaN is coded ~0 instead)
   unsigned long long m = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned long long b = __double_as_longlong(a[i]);
-    const unsigned long long e = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    const double x = a[i];
+    const unsigned long long b = __double_as_longlong(x);
+    // a NaN of either sign takes the top code (np.max propagates NaN); decoded, it is a NaN
+    const unsigned long long e = x != x ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
     m = e > m ? e : m;
   }
 #pragma unroll
@@ -1377,7 +1384,8 @@ hrf_status hrf_mask_labels(const int32_t *labels, const uint8_t *mask, int64_t n
   return HRF_OK;
 }
 
-// *max_dev (an 8-byte device word) receives max(a) as a double
+// *max_dev (an 8-byte device word) receives np.max(a) as a double: NaN when any element is a NaN of
+// either sign, and -0.0 < +0.0
 hrf_status hrf_max_f64(const double *a, int64_t n, double *max_dev, hrf_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   HRF_REQUIRE(max_dev && n >= 1 && a, "max_f64: bad arguments");

@@ -195,9 +195,11 @@ __global__ __launch_bounds__(256) void label_sums_wave_kernel(const float *__res
   }
 }
 
-// rows = labels with count > 0, ascending (regionprops order).  One workgroup.
+// rows = labels with count > 0, ascending (regionprops order).  One workgroup.  label_of_row
+// holds max_rows entries: rows past it are counted (*nrows, row_of_label) but not listed.
 __global__ __launch_bounds__(1024) void cell_rows_kernel(const unsigned long long *__restrict__ counts,
-                                                         int32_t maxlab, int32_t *__restrict__ row_of_label,
+                                                         int32_t maxlab, int32_t max_rows,
+                                                         int32_t *__restrict__ row_of_label,
                                                          int32_t *__restrict__ label_of_row,
                                                          int32_t *__restrict__ nrows) {
   __shared__ int32_t wsum[16];
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(1024) void cell_rows_kernel(const unsigned long lon
     const int32_t excl = carry + wsum[tid >> 6] + inc - v;
     if (l <= maxlab) {
       row_of_label[l] = v ? excl : -1;
-      if (v) label_of_row[excl] = (int32_t)l;
+      if (v && excl < max_rows) label_of_row[excl] = (int32_t)l;
     }
     __syncthreads();
     if (tid == 1023) carry = excl + v;
@@ -326,10 +328,12 @@ __global__ void moments_kernel(const int32_t *__restrict__ lab, int64_t H, int64
 }
 
 __device__ __forceinline__ double exact_central(int64_t A, int64_t s2, int64_t sa, int64_t sb) {
-  // (A*s2 - sa*sb) / A^2 with the numerator exact in 128-bit integers
+  // (A*s2 - sa*sb) / A^2 with the numerator exact in 128-bit integers, rounded once to a double
+  // from all 128 bits: it passes 2^63 for a one-row label wider than ~1.0e5 pixels or a filled
+  // square of side ~2200
   const __int128 num = (__int128)A * s2 - (__int128)sa * sb;
   const double A2 = (double)A * (double)A;
-  return (double)(int64_t)num / A2;
+  return (double)num / A2;
 }
 
 // the inertia eigenvalues of label l from its moments (skimage regionprops' inertia_tensor_eigvals)
@@ -468,6 +472,10 @@ hrf_status hrf_label_sums_cal(const float *stack, const int32_t *labels, int64_t
   const int vec_ok = C >= 4 && ((C * LS_P) % 4 == 0) && (((uintptr_t)stack & 15) == 0);
   const size_t shm = sizeof(float) * LS_P * C;
   const int64_t nchunks = hrf::cdiv(npix, LS_P);
+  // 64 x C floats of dynamic LDS: 128 KB at C = 512, within the CU's 160 KB but past the 64 KB a
+  // launch gets without asking
+  HRF_HIP(hipFuncSetAttribute((const void *)label_sums_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shm));
   const unsigned grid = hrf::resident_grid(label_sums_kernel, 256, shm, nchunks);
   label_sums_kernel<<<grid, 256, shm, s>>>(stack, labels, npix, C, maxlab, cal, cal_sp, cal_sc, cal_c0, cal_c1, sums,
                                            (unsigned long long *)counts, vec_ok);
@@ -481,8 +489,8 @@ hrf_status hrf_cell_table(const double *sums, const int64_t *counts, int32_t max
   hipStream_t s = (hipStream_t)stream;
   HRF_REQUIRE(maxlab >= 0 && C >= 1 && max_rows >= 0, "cell_table: bad sizes");
   HRF_REQUIRE(sums && counts && row_of_label && label_of_row && avgint && nrows_dev, "cell_table: null buffer");
-  cell_rows_kernel<<<1, 1024, 0, s>>>((const unsigned long long *)counts, maxlab, row_of_label, label_of_row,
-                                      nrows_dev);
+  cell_rows_kernel<<<1, 1024, 0, s>>>((const unsigned long long *)counts, maxlab, max_rows, row_of_label,
+                                      label_of_row, nrows_dev);
   if (max_rows > 0)
     cell_means_kernel<<<(unsigned)hrf::cdiv((int64_t)max_rows * 64, 256), 256, 0, s>>>(
         sums, (const unsigned long long *)counts, label_of_row, nrows_dev, max_rows, C, avgint, avgint_norm);

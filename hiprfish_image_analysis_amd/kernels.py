@@ -174,9 +174,10 @@ def _cal_layout(cal, H, W, C, cal_range=None):
 
 
 def channel_sum(stack, mask=None, mode=0, negate=False, cal=None, cal_range=None, out=None):
-    """np.sum(stack, axis=2) (f64, numpy pairwise order); mode 1 -> log(s+1e-2), 2 -> log10(s+1);
-    cal: np.sum(stack / cal, axis=2) (multispecies measurement.py:104-105); out: a contiguous
-    (H, W) f64 tensor to write into"""
+    """np.sum(stack, axis=2) in f64, bit for bit in numpy's pairwise order for every C in 1..512
+    (eight accumulators, blocks of at most 128, longer rows halved as numpy halves them); mode 1
+    -> log(s+1e-2), 2 -> log10(s+1); cal: np.sum(stack / cal, axis=2) (multispecies
+    measurement.py:104-105), C <= 128; out: a contiguous (H, W) f64 tensor to write into"""
     stack = _dev(stack, torch.float32, "stack")
     H, W, C = stack.shape
     if out is None:
@@ -332,6 +333,8 @@ def pad_edge_3d(a, width=5):
 
 
 def max_f64(a):
+    """np.max(a) of an f64 tensor as a one-element device tensor: NaN when any element is a NaN of
+    either sign; -0.0 orders below +0.0"""
     a = _dev(a, torch.float64, "a")
     out = torch.empty(1, dtype=torch.float64, device=a.device)
     _lib.call("hrf_max_f64", _ptr(a), a.numel(), _ptr(out), _stream())
@@ -619,7 +622,9 @@ def watershed_heap(image, markers, mask=None, negate=False):
 
 # ---- a14-a16, a20, a21, a23 -----------------------------------------------------------------
 def label_sums(stack, labels, maxlab, cal=None, cal_range=None):
-    """per-label channel sums of stack (/ cal) and pixel counts (ecoli measurement.py:147-155)"""
+    """per-label channel sums of stack (/ cal) and pixel counts (ecoli measurement.py:147-155);
+    C in 1..512, cal a plane, a per-channel vector or a full (H, W, C) array on channels
+    cal_range; labels outside 1..maxlab are background"""
     stack = _dev(stack, torch.float32, "stack")
     l = _i32(labels, "labels")
     H, W, C = stack.shape
@@ -700,6 +705,10 @@ def label_sums_lasers(lasers, shifts_dev, labels, maxlab, apply_mask=True, cal=N
 
 
 def cell_table(sums, counts, maxlab, max_rows=None):
+    """-> (row_of_label (maxlab + 1,), label_of_row, avgint, avgint_norm): rows are the labels
+    with a count, ascending; avgint = sums / counts, avgint_norm = avgint / its row maximum (NaN
+    for a row of zeros, as numpy).  max_rows (default maxlab) caps the rows returned;
+    row_of_label numbers every present label all the same."""
     C = sums.shape[1]
     dev = sums.device
     if max_rows is None:
@@ -711,16 +720,29 @@ def cell_table(sums, counts, maxlab, max_rows=None):
     nrows = torch.zeros(1, dtype=torch.int32, device=dev)
     _lib.call("hrf_cell_table", _ptr(sums), _ptr(counts), maxlab, C, max_rows, _ptr(rol), _ptr(lor), _ptr(avg),
               _ptr(avgn), _ptr(nrows), _stream())
-    n = _scalar_i32(nrows)
+    n = min(_scalar_i32(nrows), max_rows)
     return rol, lor[:n], avg[:n], avgn[:n]
 
 
-def region_props(labels, maxlab):
+def region_moments(labels, maxlab):
+    """the exact raw moments of every label 1..maxlab as a (maxlab + 1, 6) int64 table: area,
+    sum r, sum c, sum r^2, sum c^2, sum r c (row 0 and labels outside 1..maxlab: zero)"""
     l = _i32(labels, "labels")
     H, W = l.shape
     mom = torch.empty((maxlab + 1, 6), dtype=torch.int64, device=l.device)
-    props = torch.empty((maxlab + 1, 8), dtype=torch.float64, device=l.device)
     _lib.call("hrf_region_moments", _ptr(l), H, W, maxlab, _ptr(mom), _stream())
+    return mom
+
+
+def region_props(labels, maxlab):
+    """skimage regionprops per label as a (maxlab + 1, 8) f64 table: area, centroid row and
+    column, major and minor axis length, eccentricity, orientation, valid flag.  The central
+    moments are formed exactly in 128-bit integers and rounded once, so the table holds for a
+    label of any size the image can carry (a 110000-pixel row, a 2304 x 2304 square)."""
+    l = _i32(labels, "labels")
+    H, W = l.shape
+    props = torch.empty((maxlab + 1, 8), dtype=torch.float64, device=l.device)
+    mom = region_moments(l, maxlab)
     _lib.call("hrf_region_props", _ptr(mom), maxlab, _ptr(props), _stream())
     return props
 

@@ -127,7 +127,8 @@ HRF_API hrf_status hrf_label_sums_lasers(const float *const *src_host, const int
                                          int32_t apply_mask, const int32_t *labels, int32_t maxlab, const float *cal,
                                          int32_t cal_c0, int32_t cal_c1, double *sums, int64_t *counts,
                                          hrf_stream_t stream);
-/* per-pixel sum over C in numpy pairwise order (== np.sum(stack, axis=2) in f64);
+/* per-pixel sum over C in numpy pairwise order (== np.sum(stack, axis=2) in f64, bit for bit,
+ * for every C in 1..512: blocks of at most 128 values, longer rows halved as numpy halves them);
  * mode 0: sum, 1: log(sum + 1e-2) (ecoli :72), 2: log10(sum + 1) (biofilm :831);
  * mask (nullable) zeroes the sum; negate flips the sign (watershed input). */
 HRF_API hrf_status hrf_channel_sum(const float *stack, int64_t npix, int32_t C, const uint8_t *mask, int32_t mode,
@@ -159,6 +160,7 @@ HRF_API hrf_status hrf_and_u8(const uint8_t *a, const uint8_t *b, int64_t n, uin
 /* out = labels where mask, else 0 (multispecies :152 seeds * bkg) */
 HRF_API hrf_status hrf_mask_labels(const int32_t *labels, const uint8_t *mask, int64_t n, int32_t *out,
                                    hrf_stream_t stream);
+/* *max_dev = np.max(a), n >= 1: NaN when any element is a NaN of either sign; -0.0 < +0.0 */
 HRF_API hrf_status hrf_max_f64(const double *a, int64_t n, double *max_dev, hrf_stream_t stream);
 HRF_API hrf_status hrf_div_scalar_f64(const double *a, int64_t n, const double *divisor_dev, double *out,
                                       hrf_stream_t stream);
@@ -405,12 +407,16 @@ HRF_API hrf_status hrf_label_sums(const float *stack, const int32_t *labels, int
                                   const float *cal, int32_t cal_c0, int32_t cal_c1, double *sums, int64_t *counts,
                                   hrf_stream_t stream);
 /* the same with a strided calibration: channels [c0, c1) of pixel p divided by
- * cal[p*cal_sp + c*cal_sc] (plane: sp 1, sc 0; per channel: sp 0, sc 1; full: sp C, sc 1) */
+ * cal[p*cal_sp + c*cal_sc] (plane: sp 1, sc 0; per channel: sp 0, sc 1; full: sp C, sc 1).
+ * C in 1..512 (the wave kernel to 128, the LDS kernel above), any stack alignment; labels
+ * outside 1..maxlab are background. */
 HRF_API hrf_status hrf_label_sums_cal(const float *stack, const int32_t *labels, int64_t npix, int32_t C,
                                       int32_t maxlab, const float *cal, int64_t cal_sp, int32_t cal_sc, int32_t cal_c0,
                                       int32_t cal_c1, double *sums, int64_t *counts, hrf_stream_t stream);
 /* rows = present labels ascending (regionprops order); avgint = sums/counts,
- * avgint_norm = avgint / rowmax (ecoli :157, classify_spectra.py:27). */
+ * avgint_norm = avgint / rowmax (ecoli :157, classify_spectra.py:27; a row of zeros: NaN, as
+ * numpy).  label_of_row, avgint and avgint_norm hold max_rows rows and receive the first
+ * max_rows of them; row_of_label[maxlab+1] and *nrows_dev cover every present label. */
 HRF_API hrf_status hrf_cell_table(const double *sums, const int64_t *counts, int32_t maxlab, int32_t C,
                                   int32_t max_rows, int32_t *row_of_label, int32_t *label_of_row, double *avgint,
                                   double *avgint_norm, int32_t *nrows_dev, hrf_stream_t stream);
@@ -418,7 +424,8 @@ HRF_API hrf_status hrf_cell_table(const double *sums, const int64_t *counts, int
 HRF_API hrf_status hrf_region_moments(const int32_t *labels, int64_t H, int64_t W, int32_t maxlab, int64_t *mom,
                                       hrf_stream_t stream);
 /* regionprops area, centroid, major/minor axis, eccentricity, orientation
- * (classify_spectra.py:38-46): props[(maxlab+1)*8] */
+ * (classify_spectra.py:38-46): props[(maxlab+1)*8].  The central moments' numerators are exact
+ * 128-bit integers rounded once to f64, so the table holds for a label of any size (H*W < 2^31). */
 HRF_API hrf_status hrf_region_props(const int64_t *mom, int32_t maxlab, double *props, hrf_stream_t stream);
 /* E. coli per-cell filter (ecoli measurement.py:116-126): cells with minor axis in
  * [minor_lo, minor_hi] keep their 2x-cross-eroded interior, others vanish. */
