@@ -17,8 +17,10 @@
 //     registered stack is produced (pixtable.hpp) -- the timed path;
 //   * the certificate: the best row rescored in f64 as the restatement does; it is the answer when
 //     its distance beats the runner-up bound by the screen's proven error bound (screen_eps);
-//   * the list pass: every pixel the certificate leaves (ties, near-ties, non-finite values) is
-//     scored against all rows in f32 with its own bound, the rows within it rescored in f64.
+//   * the list pass: for every pixel the certificate leaves (ties, near-ties, non-finite values)
+//     the rows that can be the answer -- from an MFMA sweep of the 16x16x32 library image against a
+//     threshold proven from the screen's bound, or from an f32 scoring of all rows with its own
+//     bound -- are rescored in f64.
 // Per cell (reference semantics, gated by presence flags): f64, exact channel order of the
 // restatement, CB cells per workgroup -- bit-identical to oracle_segcos.
 //

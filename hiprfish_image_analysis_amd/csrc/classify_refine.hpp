@@ -226,7 +226,10 @@ __device__ __forceinline__ void refine_pixels64(const RefineArgs &A, int C, cons
     int base = 0;
     if (lane == __ffsll((long long)m) - 1) base = atomicAdd(A.cnt, __popcll(m));
     base = __shfl(base, __ffsll((long long)m) - 1, 64);
-    if (listed) A.list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)p;
+    if (listed) {
+      A.list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)p;
+      if (write_idx) best_idx[p] = b1;  // the list pass's reference row (the unfused screen stored it)
+    }
   }
 }
 

@@ -108,6 +108,11 @@ struct RefineArgs {
   double eps_base, eps_zero;
   int32_t *list, *cnt;
   Bounds bd;  // (kernel-argument memory: indexed by a runtime segment without a scratch copy)
+  // the list pass's candidate sweep: the library's 16x16x32 MFMA image (the start of refx), its row
+  // pitch in bytes and its rows; null where the screen's table is no such image (the list pass then
+  // scores every row in f32)
+  const void *img;
+  int32_t img_rowb, img_rows;
 };
 
 struct ScreenEps {

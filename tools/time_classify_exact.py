@@ -1,6 +1,7 @@
 """Per-pixel classifier on one bench-like 2048^2 x 95 tile (R = 1023): the w16t screen from the
 assembly's pixel table, the f64 refine reading the five shifted acquisitions, and the number of
-pixels the certificate left to the list pass.  HIP events on the current stream.
+pixels the certificate left to the list pass, with the list pass's own time.  HIP events on the
+current stream.
 python tools/time_classify_exact.py [reps]"""
 import os
 import sys
@@ -44,6 +45,15 @@ def main():
         K.classify_refine(pt.source, refx, R, S.ECOLI_BOUNDS, 3, i2, d2, sec)
     t_copy = ev(lambda: (i2.copy_(idx), d2.copy_(dist)), n)
     t_ref = ev(refine, n) - t_copy
+    # the list pass on its own: the same refine with every runner-up bound at -inf certifies every
+    # finite pixel, so its list pass finds a count of zero and costs its launch
+    none = torch.full_like(sec, float("-inf"))
+
+    def refine_nolist():
+        i2.copy_(idx)
+        d2.copy_(dist)
+        K.classify_refine(pt.source, refx, R, S.ECOLI_BOUNDS, 3, i2, d2, none)
+    t_cert = ev(refine_nolist, n) - t_copy
     i2.copy_(idx)
     d2.copy_(dist)
     listed = K.classify_refine(pt.source, refx, R, S.ECOLI_BOUNDS, 3, i2, d2, sec, want_listed=True)
@@ -62,6 +72,8 @@ def main():
     st = K.classify_refine(pt.source, refx, R, S.ECOLI_BOUNDS, 3, i2, d2, sec, want_listed="stats")
     print("list pass: %d pixels, %d sparse f64 candidates (%.1f per pixel), %d pixels scored in full"
           % (st[0], st[1], st[1] / max(st[0], 1), st[2]))
+    print("certificate %.3f ms (refine with an empty list) | list pass %.3f ms (refine - certificate)"
+          % (t_cert, t_ref - t_cert))
     eps = K.classify_screen_eps(95, S.ECOLI_BOUNDS, R, 3)
     print("bounds (score units): screen %.3e, per zero segment %.3e, list pass %.3e" % eps)
 
