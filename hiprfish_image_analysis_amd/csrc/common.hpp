@@ -174,6 +174,10 @@ hrf_status watershed_ex_extra(const double *image, int32_t negate, const int32_t
                               int64_t H, int64_t W, int32_t *out_labels, void *state_ws, int32_t *flag_ws,
                               int32_t max_passes, int32_t *passes_host, int32_t *ties_host, hipStream_t s,
                               const ZeroPub *extra);
+// skimage's heap flood on an (X, Y, Z) volume, six neighbours, one workgroup (watershed.hip; the
+// tie path of volume.hip's hrf_watershed3)
+hrf_status heap_flood3(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask, int64_t X,
+                       int64_t Y, int64_t Z, int32_t *out_labels, hipStream_t s);
 // device address of pinned host memory from hipHostMalloc (nullptr when it has none)
 int32_t *mapped(int32_t *host);
 // hipHostMalloc with the flags zero_publish's host slots need (mapped, coherent)

@@ -771,6 +771,99 @@ hrf_status heap_flood(const double *image, int32_t negate, const int32_t *marker
   return HRF_OK;
 }
 
+// ws_heap_flood_kernel on an (X, Y, Z) volume (volume.hip's tie path): the same heap and the same
+// two phases, six neighbours visited in raster-offset order -X, -Y, -Z, +Z, +Y, +X, which on a
+// volume with one axis of extent 1 is the 2-D kernel's up, left, right, down.  A kernel of its own,
+// so the 2-D kernel's code does not change.
+template <bool HASMASK>
+__global__ __launch_bounds__(1024) void ws_heap_flood3_kernel(const double *__restrict__ f, int negate,
+                                                              const int32_t *__restrict__ markers,
+                                                              const uint8_t *__restrict__ mask, int32_t X, int32_t Y,
+                                                              int32_t Z, int32_t *__restrict__ out,
+                                                              HeapItem *__restrict__ heap,
+                                                              int32_t *__restrict__ list) {
+  extern __shared__ HeapItem heap_smem[];
+  __shared__ int32_t wsum[16];
+  __shared__ int32_t base_s;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int32_t n = X * Y * Z;
+  if (tid == 0) base_s = 0;
+  __syncthreads();
+  for (int32_t c0 = 0; c0 < n; c0 += 1024) {
+    const int32_t i = c0 + tid;  // c0 <= 2^31 - 1024: no overflow
+    int32_t m = 0;
+    if (i < n) {
+      m = (!mask || mask[i]) ? markers[i] : 0;
+      out[i] = m;
+    }
+    const uint64_t bal = __ballot(m != 0);
+    if (lane == 0) wsum[wv] = __popcll(bal);
+    __syncthreads();
+    int32_t off = base_s;
+    for (int k = 0; k < wv; ++k) off += wsum[k];
+    if (m) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+    __syncthreads();
+    if (tid == 0) {
+      int32_t t = base_s;
+      for (int k = 0; k < 16; ++k) t += wsum[k];
+      base_s = t;
+    }
+    __syncthreads();
+    if (c0 > n - 1024) break;  // the last chunk: c0 + 1024 could overflow
+  }
+  if (wv != 0) return;
+  __threadfence_block();
+  HeapView h{(HRF_LDS heap_u4 *)heap_smem, heap};
+  const int32_t nm = heap_uni(base_s);
+  int32_t hn = 0;
+  for (int32_t k = 0; k < nm; ++k) {
+    const int32_t i = heap_uni(list[k]);
+    const double fv = heap_uni(f[i]);
+    heap_push_w(h, hn, HeapItem{negate ? -fv : fv, 0u, i}, lane);
+  }
+  uint32_t age = 1;
+  const int32_t sY = Z, sX = Y * Z;
+  while (hn > 0) {
+    const int32_t x = heap_uni(h.get(0).idx);
+    HeapItem lastg{0.0, 0u, 0};
+    if (hn - 1 >= HEAP_LDS) lastg = h.g[hn - 1];
+    const int32_t px = x / sX, rem = x - px * sX, py = rem / sY, pz = rem - py * sY;
+    // lane d < 6 loads neighbour d's state, read before any of them is written (distinct voxels);
+    // a neighbour off the volume reads the voxel itself and is never free
+    const int dn = lane < 6 ? lane : 0;
+    const bool okd = dn == 0 ? px > 0 : dn == 1 ? py > 0 : dn == 2 ? pz > 0 : dn == 3 ? pz + 1 < Z
+                   : dn == 4 ? py + 1 < Y : px + 1 < X;
+    const int32_t nbd = dn == 0 ? x - sX : dn == 1 ? x - sY : dn == 2 ? x - 1 : dn == 3 ? x + 1
+                      : dn == 4 ? x + sY : x + sX;
+    const int32_t q = okd ? nbd : x;
+    const uint32_t mq = HASMASK ? mask[q] : 1u;
+    const int32_t oq = out[q];
+    const double vq = f[q];
+    const int32_t labv = out[x];
+    hn -= 1;
+    if (hn > 0 && hn < HEAP_LDS) {
+      const HeapItem last = __builtin_bit_cast(HeapItem, h.l[hn]);
+      heap_sift_down_w<true>(h, hn, HeapItem{heap_uni(last.v), (uint32_t)heap_uni((int32_t)last.age), heap_uni(last.idx)},
+                             lane);
+    } else if (hn > 0) {
+      heap_sift_down_w<false>(
+          h, hn, HeapItem{heap_uni(lastg.v), (uint32_t)heap_uni((int32_t)lastg.age), heap_uni(lastg.idx)}, lane);
+    }
+    const unsigned long long fm = __ballot(lane < 6 && okd && mq != 0u && oq == 0);
+    const int32_t lab = heap_uni(labv);
+    const double vn = negate ? -vq : vq;
+#pragma unroll
+    for (int dd = 0; dd < 6; ++dd) {
+      if (!((fm >> dd) & 1ull)) continue;
+      const int32_t nb = dd == 0 ? x - sX : dd == 1 ? x - sY : dd == 2 ? x - 1 : dd == 3 ? x + 1
+                       : dd == 4 ? x + sY : x + sX;
+      age += 1;
+      heap_push_w(h, hn, HeapItem{heap_lane(vn, dd), age, nb}, lane);
+    }
+    if ((fm >> lane) & 1ull) out[nbd] = lab;
+  }
+}
+
 int64_t walker_bytes(int32_t cap, int32_t hcap, int32_t gcap) {
   int64_t b = 5 * (int64_t)cap * 4 + (int64_t)hcap * 12 + (int64_t)gcap * (8 + 4 + 4 + 1);
   return (b + 255) & ~(int64_t)255;
@@ -974,6 +1067,42 @@ hrf_status hrf::watershed_ex_extra(const double *image, int32_t negate, const in
   if (layout > 0)
     if (hrf_status r = heap_flood(image, negate, markers, mask, H, W, out_labels, s)) return r;
   if (passes_host) *passes_host = passes;
+  return HRF_OK;
+}
+
+// the heap flood of an (X, Y, Z) volume, X*Y*Z < 2^31 - 2 (checked by the caller, volume.hip)
+hrf_status hrf::heap_flood3(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask,
+                            int64_t X, int64_t Y, int64_t Z, int32_t *out, hipStream_t s) {
+  const int64_t n = X * Y * Z;
+  HRF_REQUIRE(n < ((int64_t)1 << 31) - 2, "watershed heap replay: volume too large");
+  if (n == 0) return HRF_OK;
+  hrf::StreamBuf<char> scratch;
+  HRF_HIP(scratch.alloc((size_t)heap_flood_scratch_bytes(n), s));
+  static const bool attr = [] {
+    return hipFuncSetAttribute((const void *)ws_heap_flood3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)HEAP_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute((const void *)ws_heap_flood3_kernel<false>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAP_LDS_BYTES) == hipSuccess;
+  }();
+  if (!attr) {
+    ::hrf::set_error("watershed heap replay: cannot reserve %d bytes of LDS", (int)HEAP_LDS_BYTES);
+    return HRF_EHIP;
+  }
+  char *base = scratch;
+  HeapItem *hp = (HeapItem *)base;
+  int32_t *lp = (int32_t *)(base + (n + 2) * 16);
+  if (mask)
+    ws_heap_flood3_kernel<true><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)X, (int32_t)Y,
+                                                                (int32_t)Z, out, hp, lp);
+  else
+    ws_heap_flood3_kernel<false><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)X, (int32_t)Y,
+                                                                 (int32_t)Z, out, hp, lp);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
+    return HRF_EHIP;
+  }
+  HRF_HIP(scratch.free());
   return HRF_OK;
 }
 

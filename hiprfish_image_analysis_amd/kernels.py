@@ -620,6 +620,128 @@ def watershed_heap(image, markers, mask=None, negate=False):
     return out
 
 
+# ---- 3-D segmentation stages (volume.hip) ---------------------------------------------------
+def _xyz(t, name):
+    """(X, Y, Z) of a volume; the library's size limit is checked before any output is allocated"""
+    if t.dim() != 3:
+        raise ValueError("%s: an (X, Y, Z) volume expected, got shape %s" % (name, tuple(t.shape)))
+    X, Y, Z = (int(d) for d in t.shape)
+    if X * Y * Z >= 2 ** 31 - 2:
+        raise ValueError("%s: volume too large (%d x %d x %d, limit 2^31 - 2 voxels)" % (name, X, Y, Z))
+    return X, Y, Z
+
+
+def label3(img, conn=3, return_num=True):
+    """skimage.morphology.label / scipy.ndimage.label on an (X, Y, Z) volume: conn 1, 2, 3 = 6-, 18-,
+    26-connectivity (skimage's 3-D default, biofilm :844), raster-first numbering"""
+    X, Y, Z = _xyz(img, "label3")
+    t, dt = _img(img)
+    dev = t.device
+    n = X * Y * Z
+    labels = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
+    parent = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    blk = torch.empty((n + 1023) // 1024 + 1, dtype=torch.int32, device=dev)
+    nlab = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("hrf_label3", _ptr(t), dt, X, Y, Z, conn, _ptr(labels), _ptr(parent), _ptr(blk), _ptr(nlab), _stream())
+    if return_num:
+        return labels, _scalar_i32(nlab)
+    return labels, nlab
+
+
+def binary_erosion3(mask, border_value=0):
+    """binary erosion with the 6-neighbour cross; border_value 0 is scipy.ndimage's default (the
+    biofilm script's), 1 skimage's"""
+    m = _u8(mask, "mask")
+    X, Y, Z = _xyz(m, "binary_erosion3")
+    out = torch.empty_like(m)
+    _lib.call("hrf_binary_erosion3", _ptr(m), X, Y, Z, int(border_value), _ptr(out), _stream())
+    return out
+
+
+def binary_dilation3(mask):
+    m = _u8(mask, "mask")
+    X, Y, Z = _xyz(m, "binary_dilation3")
+    out = torch.empty_like(m)
+    _lib.call("hrf_binary_dilation3", _ptr(m), X, Y, Z, _ptr(out), _stream())
+    return out
+
+
+def binary_opening3(mask, border_value=0):
+    """scipy.ndimage.binary_opening (biofilm :32, :839): dilation(erosion(border_value=0))"""
+    return binary_dilation3(binary_erosion3(mask, border_value))
+
+
+def fill_holes3(mask):
+    """scipy.ndimage.binary_fill_holes on a volume (background 6-connected from the faces)"""
+    m = _u8(mask, "mask")
+    X, Y, Z = _xyz(m, "fill_holes3")
+    out = torch.empty_like(m)
+    parent = torch.empty(max(m.numel(), 1), dtype=torch.int32, device=m.device)
+    flag = torch.empty(max(m.numel(), 1), dtype=torch.int32, device=m.device)
+    _lib.call("hrf_fill_holes3", _ptr(m), X, Y, Z, _ptr(out), _ptr(parent), _ptr(flag), _stream())
+    return out
+
+
+def remove_small_objects3(mask, min_size=64, conn=1):
+    """skimage.morphology.remove_small_objects on a bool volume (biofilm :840)"""
+    m = _u8(mask, "mask")
+    X, Y, Z = _xyz(m, "remove_small_objects3")
+    out = torch.empty_like(m)
+    parent = torch.empty(max(m.numel(), 1), dtype=torch.int32, device=m.device)
+    size = torch.empty(max(m.numel(), 1), dtype=torch.int32, device=m.device)
+    _lib.call("hrf_remove_small_objects_mask3", _ptr(m), X, Y, Z, min_size, conn, _ptr(out), _ptr(parent),
+              _ptr(size), _stream())
+    return out
+
+
+def log10p1(x):
+    """np.log10(x + 1) on f64 with the correctly rounded log10 (biofilm :845)"""
+    x = _dev(x, torch.float64, "x")
+    out = torch.empty_like(x)
+    _lib.call("hrf_log10p1_f64", _ptr(x), x.numel(), _ptr(out), _stream())
+    return out
+
+
+def watershed3(image, markers, mask=None, negate=False, ties: list | None = None, max_passes=100000):
+    """skimage.morphology.watershed(+/-image, markers, mask=mask) on an (X, Y, Z) volume,
+    connectivity 1.  `ties` (a list) receives [contested voxels, 1 if the serial heap flood ran,
+    relaxation passes] (hrf_watershed3)."""
+    import ctypes
+    image = _dev(image, torch.float64, "image")
+    mk = _i32(markers, "markers")
+    X, Y, Z = _xyz(image, "watershed3")
+    if tuple(mk.shape) != (X, Y, Z):
+        raise ValueError("watershed3: markers must have the image's shape")
+    m = _u8(mask, "mask") if mask is not None else None
+    if m is not None and tuple(m.shape) != (X, Y, Z):
+        raise ValueError("watershed3: mask must have the image's shape")
+    out = torch.empty((X, Y, Z), dtype=torch.int32, device=image.device)
+    nb = _lib.lib().hrf_watershed3_workspace_bytes(X, Y, Z)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=image.device)
+    fl = torch.empty(8, dtype=torch.int32, device=image.device)
+    passes = ctypes.c_int32(0)
+    st = (ctypes.c_int32 * 3)()
+    _lib.call("hrf_watershed3", _ptr(image), int(negate), _ptr(mk), _ptr(m), X, Y, Z, _ptr(out), _ptr(ws), _ptr(fl),
+              max_passes, ctypes.addressof(passes), ctypes.addressof(st), _stream())
+    if ties is not None:
+        ties[:] = list(st)
+    return out
+
+
+def watershed3_heap(image, markers, mask=None, negate=False):
+    """skimage's heap flood itself on a volume, one workgroup (hrf_watershed3_heap): the tie path of
+    watershed3(); serial"""
+    image = _dev(image, torch.float64, "image")
+    mk = _i32(markers, "markers")
+    X, Y, Z = _xyz(image, "watershed3_heap")
+    if tuple(mk.shape) != (X, Y, Z):
+        raise ValueError("watershed3_heap: markers must have the image's shape")
+    m = _u8(mask, "mask") if mask is not None else None
+    out = torch.empty((X, Y, Z), dtype=torch.int32, device=image.device)
+    _lib.call("hrf_watershed3_heap", _ptr(image), int(negate), _ptr(mk), _ptr(m), X, Y, Z, _ptr(out), _stream())
+    return out
+
+
 # ---- a14-a16, a20, a21, a23 -----------------------------------------------------------------
 def label_sums(stack, labels, maxlab, cal=None, cal_range=None):
     """per-label channel sums of stack (/ cal) and pixel counts (ecoli measurement.py:147-155);

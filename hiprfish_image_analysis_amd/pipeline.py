@@ -202,11 +202,95 @@ def enhance_volume(stack: torch.Tensor, v3: bool = False) -> torch.Tensor:
     """biofilm :808-817 on the registered (X, Y, Z, C) volume: channel sum (numpy order),
     / max, edge pad 5, line_profile_memory_efficient_v2 (v3 with `v3`) and the
     average * (1 - quartile coefficient) post-chain -> image_final (X+10, Y+10, Z+10) f64"""
+    return _enhance_norm(volume_sum_norm(stack), v3)
+
+
+def volume_sum_norm(stack: torch.Tensor) -> torch.Tensor:
+    """biofilm :808-809: the channel sum of the registered (X, Y, Z, C) volume (numpy order) over
+    its maximum -> image_registered_sum (X, Y, Z) f64"""
     X, Y, Z, C = stack.shape
     s = K.channel_sum(stack.reshape(X * Y, Z, C)).reshape(X, Y, Z)     # :808
-    s = K.div_scalar(s, K.max_f64(s))                                   # :809
+    return K.div_scalar(s, K.max_f64(s))                                # :809
+
+
+def _enhance_norm(s: torch.Tensor, v3: bool = False) -> torch.Tensor:
     pad = K.pad_edge_3d(s, 5)                                           # :810
     return K.enhance_3d_v3(pad) if v3 else K.enhance_3d(pad)            # :811-817
+
+
+# --------------------------------------------------------------------------------------------
+# Biofilm 3-D segmentation (hiprfish_imaging_biofilm_analysis.py:818-859, :489-499)
+# --------------------------------------------------------------------------------------------
+def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None = None, adjacency: bool = False):
+    """biofilm :818-859 on image_final and the normalised registered sum, both (X, Y, Z) f64.
+    -> (segmentation int32 relabelled 1..n, n, final_bkg_filtered f64[, adjacency_seg, n_adj])
+
+    The KMeans cluster choices, read off the reference's comparisons of cluster means:
+    :819-828 (k = 2 on final > 0) takes the cluster with the larger mean, sklearn's cluster 0 when
+    the comparison is not `i0 < i1` -- every fitted value is positive, so this is rule 2;
+    :830-838 (k = 3, same values, the sort shared) takes argmax of the means -- rule 0;
+    :846-854 (k = 2 on log10(sum + 1), all voxels) averages the positive sums of each cluster and
+    falls to cluster 0 on a NaN mean, log10(sum + 1) > 0 exactly where sum > 0 -- rule 1.
+    adjacency: also the flood of :489, :497-499, watershed(-(reg_sum * bkg), seeds * bkg, mask=bkg),
+    relabelled -- unlike :858, where the seeds are the label of the very mask passed in and no
+    voxel is left to flood, this one does the flood's real work."""
+    final = K._dev(final, torch.float64, "final")
+    reg_sum = K._dev(reg_sum, torch.float64, "reg_sum")
+    if final.dim() != 3 or final.shape != reg_sum.shape:
+        raise ValueError("segment_volume: final and reg_sum must be (X, Y, Z) volumes of one shape")
+    pos = final > 0
+    share: dict = {}
+    _, rough, cen2, _ = K.kmeans_1d(final, 2, valid=pos, want_labels=False, share=share, rule=2)    # :818-828
+    _, rsf, cen3, _ = K.kmeans_1d(final, 3, valid=pos, want_labels=False, share=share, rule=0)      # :829-838
+    opened = K.binary_opening3(rsf, border_value=0)                                 # :839 scipy's opening
+    small = K.remove_small_objects3(opened, 10, conn=1)                             # :840
+    bfh = K.fill_holes3(small)                                                      # :841
+    rough_bfh = K.fill_holes3(rough)                                                # :842
+    wmask = K.and_mask(bfh, rough_bfh)                                              # :843
+    seeds, nseeds = K.label3(wmask, conn=3)                                         # :844
+    logsum = K.log10p1(reg_sum)              # :845, the correctly rounded log10 of channel_sum(mode=2)
+    _, bkg, cenb, _ = K.kmeans_1d(logsum, 2, want_labels=False, rule=1)             # :846-854
+    final_bkg = K.mask_mul(final, bkg)                                              # :855
+    seeds_bkg = K.mask_labels(seeds, bkg)                                           # :856
+    wmask_bkg = K.and_mask(wmask, bkg)                                              # :857
+    ties: list = []
+    ws = K.watershed3(final_bkg, seeds_bkg, wmask_bkg, negate=True, ties=ties)      # :858
+    seg, n = K.relabel_sequential(ws, nseeds)                                       # :859
+    out = (seg, n, final_bkg)
+    adj = None
+    if adjacency:
+        ties_adj: list = []
+        sum_bkg = K.mask_mul(reg_sum, bkg)                                          # :489
+        aws = K.watershed3(sum_bkg, seeds_bkg, bkg, negate=True, ties=ties_adj)     # :497
+        adj, n_adj = K.relabel_sequential(aws, nseeds)                              # :499
+        out = out + (adj, n_adj)
+    if keep is not None:
+        keep.update(rough_mask=rough, rsf=rsf, opened=opened, small=small, bfh=bfh, rough_bfh=rough_bfh,
+                    watershed_mask=wmask, seeds=seeds, nseeds=nseeds, logsum=logsum, bkg_mask=bkg,
+                    final_bkg=final_bkg, seeds_bkg=seeds_bkg, watershed_mask_bkg=wmask_bkg, watershed=ws,
+                    centers2=cen2, centers3=cen3, centers_bkg=cenb, ties=ties)
+        if adjacency:
+            keep.update(adjacency_watershed=aws, adjacency_seg=adj, ties_adjacency=ties_adj)
+    return out
+
+
+def segment_volume_stack(stack: torch.Tensor, keep: dict | None = None, adjacency: bool = False, v3: bool = False):
+    """biofilm :808-859 from the registered (X, Y, Z, C) volume: enhance_volume, then
+    segment_volume on image_final and the normalised sum it was made from"""
+    s = volume_sum_norm(stack)
+    final = _enhance_norm(s, v3)
+    if keep is not None:
+        keep.update(reg_sum=s, final=final)
+    return segment_volume(final, s, keep, adjacency)
+
+
+def measure_volume(stack: torch.Tensor, seg: torch.Tensor, n: int):
+    """per-label mean spectra of a segmented (X, Y, Z, C) volume (regionprops mean_intensity per
+    channel) and their row-max normalisation, through the flat label_sums / cell_table"""
+    X, Y, Z, C = stack.shape
+    sums, counts = K.label_sums(stack.reshape(X * Y, Z, C), seg.reshape(X * Y, Z), n)
+    _, lor, avgint, avgint_norm = K.cell_table(sums, counts, n)
+    return Measurement(seg, n, lor, avgint, avgint_norm)
 
 
 # --------------------------------------------------------------------------------------------

@@ -330,6 +330,55 @@ HRF_API hrf_status hrf_watershed_heap(const double *image, int32_t negate, const
                                       const uint8_t *mask, int64_t H, int64_t W, int32_t *out_labels,
                                       hrf_stream_t stream);
 
+/* ==== 3-D segmentation stages (volume.hip) ================================================
+ * biofilm_analysis.py:818-859 (generate_3d_segmentation_memory_efficient) and :489-499.
+ * Volumes are (X, Y, Z), row-major with Z fastest: voxel p = (x * Y + y) * Z + z.  Every entry
+ * requires X * Y * Z < 2^31 - 2 (HRF_EINVAL above).  Numbering, component sizes and relabelling
+ * are hrf_cc_number, hrf_cc_sizes and hrf_relabel_sequential, which are flat in n.
+ * conn: 1 = 6-, 2 = 18-, 3 = 26-connectivity (skimage.morphology.label's 3-D default, :844).
+ * dtype as hrf_cc_roots.  parent[p] = minimum raster index of p's component, -1 for background. */
+HRF_API hrf_status hrf_cc_roots3(const void *img, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int32_t conn,
+                                 int32_t *parent, hrf_stream_t stream);
+/* raster-first numbering, bit-identical to scipy.ndimage.label / skimage label; workspaces as
+ * hrf_label with n = X * Y * Z */
+HRF_API hrf_status hrf_label3(const void *img, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int32_t conn,
+                              int32_t *labels, int32_t *parent_ws, int32_t *blk_ws, int32_t *nlab_dev,
+                              hrf_stream_t stream);
+/* binary erosion / dilation with the 6-neighbour cross.  border_value is what the erosion reads
+ * outside the volume: scipy.ndimage's (the biofilm script's binary_opening, :32, :839) uses 0,
+ * skimage's 1. */
+HRF_API hrf_status hrf_binary_erosion3(const uint8_t *mask, int64_t X, int64_t Y, int64_t Z, int32_t border_value,
+                                       uint8_t *out, hrf_stream_t stream);
+HRF_API hrf_status hrf_binary_dilation3(const uint8_t *mask, int64_t X, int64_t Y, int64_t Z, uint8_t *out,
+                                        hrf_stream_t stream);
+/* scipy.ndimage.binary_fill_holes (:841-842): the background is 6-connected from the volume's
+ * faces, so a cavity open only across an edge or a corner is filled; parent_ws, flag_ws n int32 */
+HRF_API hrf_status hrf_fill_holes3(const uint8_t *mask, int64_t X, int64_t Y, int64_t Z, uint8_t *out,
+                                   int32_t *parent_ws, int32_t *flag_ws, hrf_stream_t stream);
+/* skimage.morphology.remove_small_objects on a bool volume (:840, connectivity 1) */
+HRF_API hrf_status hrf_remove_small_objects_mask3(const uint8_t *mask, int64_t X, int64_t Y, int64_t Z,
+                                                  int64_t min_size, int32_t conn, uint8_t *out, int32_t *parent_ws,
+                                                  int32_t *size_ws, hrf_stream_t stream);
+/* out = log10(x + 1) on f64 (:845), the correctly rounded log10 of hrf_channel_sum's mode 2 */
+HRF_API hrf_status hrf_log10p1_f64(const double *x, int64_t n, double *out, hrf_stream_t stream);
+/* skimage.morphology.watershed(+/-image, markers, mask) on a volume (:858, :497), connectivity 1,
+ * neighbours in raster-offset order -X, -Y, -Z, +Z, +Y, +X (the 2-D order when one axis has extent
+ * 1).  The relaxation of hrf_watershed_ex runs in LDS bricks; when no voxel's least-key labelled
+ * neighbours carry different labels its labels are final, otherwise the whole volume is flooded by
+ * hrf_watershed3_heap's kernel (one workgroup, serial) and those labels are returned.
+ * state_ws: hrf_watershed3_workspace_bytes device bytes; flag_ws: >= 8 int32.  ties_host (nullable,
+ * 3 int32): contested voxels, 1 if the heap flood ran, relaxation passes.  When every in-mask voxel
+ * is a marker (the call at :858) no pass runs.  Synchronises once after the initial state, then
+ * after 8 passes and per 4; HRF_EINVAL if not converged within max_passes. */
+HRF_API int64_t hrf_watershed3_workspace_bytes(int64_t X, int64_t Y, int64_t Z);
+HRF_API hrf_status hrf_watershed3(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask,
+                                  int64_t X, int64_t Y, int64_t Z, int32_t *out_labels, void *state_ws,
+                                  int32_t *flag_ws, int32_t max_passes, int32_t *passes_host, int32_t *ties_host,
+                                  hrf_stream_t stream);
+HRF_API hrf_status hrf_watershed3_heap(const double *image, int32_t negate, const int32_t *markers,
+                                       const uint8_t *mask, int64_t X, int64_t Y, int64_t Z, int32_t *out_labels,
+                                       hrf_stream_t stream);
+
 /* ==== native segmentation drivers (segment.hip) ==========================================
  * One call runs a whole segmentation chain -- the same library calls, in the same order, as
  * pipeline.segment_ecoli / segment_multispecies -- with device buffers owned by a context
