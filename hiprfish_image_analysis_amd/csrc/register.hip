@@ -274,9 +274,125 @@ __global__ __launch_bounds__(256) void shifts_batch_kernel(const Best *__restric
   }
 }
 
+// ---- volumes: register_translation on (X, Y, Z) f64 (biofilm :143, :537) -----------------
+// One 3-D plan pair per (device, X, Y, Z); the reference volume's transform is taken once and
+// every target reuses it.  The targets go one at a time: a spectrum and a surface of a
+// 1024 x 1024 x 64 volume are half a GB each.
+std::map<std::tuple<int, int64_t, int64_t, int64_t>, Plans> g_plans3;
+
+hrf_status get_plans3(int64_t X, int64_t Y, int64_t Z, Plans *out) {
+  int dev = 0;
+  HRF_HIP(hipGetDevice(&dev));
+  auto key = std::make_tuple(dev, X, Y, Z);
+  auto it = g_plans3.find(key);
+  if (it != g_plans3.end()) {
+    *out = it->second;
+    return HRF_OK;
+  }
+  Plans p{};
+  size_t wf = 0, wi = 0;
+  HRF_FFT(hipfftCreate(&p.fwd));
+  HRF_FFT(hipfftCreate(&p.inv));
+  HRF_FFT(hipfftSetAutoAllocation(p.fwd, 0));
+  HRF_FFT(hipfftSetAutoAllocation(p.inv, 0));
+  HRF_FFT(hipfftMakePlan3d(p.fwd, (int)X, (int)Y, (int)Z, HIPFFT_D2Z, &wf));
+  HRF_FFT(hipfftMakePlan3d(p.inv, (int)X, (int)Y, (int)Z, HIPFFT_Z2D, &wi));
+  p.work = std::max(wf, wi);
+  g_plans3[key] = p;
+  *out = p;
+  return HRF_OK;
+}
+
+// b = a * conj(b) in place (numpy: src_freq * target_freq.conj())
+__global__ void xcorr_product_inplace_kernel(const hipfftDoubleComplex *__restrict__ a, int64_t n,
+                                             hipfftDoubleComplex *__restrict__ b) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const hipfftDoubleComplex x = a[i], y = b[i];
+    b[i] = make_hipDoubleComplex(x.x * y.x + x.y * y.y, x.y * y.x - x.x * y.y);
+  }
+}
+
+// the peak of one surface from its partials -> the wrapped (clamped) (sx, sy, sz) of one target
+__global__ __launch_bounds__(256) void shift3_kernel(const Best *__restrict__ part, int nparts, int64_t X, int64_t Y,
+                                                     int64_t Z, int32_t clamp, int32_t *__restrict__ shift,
+                                                     int32_t *__restrict__ shift_ref) {
+  Best b{-1.0, INT64_MAX};
+  for (int i = threadIdx.x; i < nparts; i += 256) b = better(b, part[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Best q{__shfl_xor(b.v, o, 64), (int64_t)__shfl_xor((long long)b.i, o, 64)};
+    b = better(b, q);
+  }
+  __shared__ Best red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 1; q < 4; ++q) b = better(b, red[q]);
+    int64_t s[3] = {b.i / (Y * Z), (b.i / Z) % Y, b.i % Z};
+    const int64_t n[3] = {X, Y, Z};
+    for (int a = 0; a < 3; ++a) {
+      if (s[a] > n[a] / 2) s[a] -= n[a];  // midpoints = fix(n / 2)
+      if (clamp >= 0 && (s[a] > clamp || s[a] < -clamp)) s[a] = 0;
+      shift[a] = (int32_t)s[a];
+    }
+    if (shift_ref) shift_ref[0] = shift_ref[1] = shift_ref[2] = 0;
+  }
+}
+
+bool sizes3_ok(int32_t nimg, int64_t X, int64_t Y, int64_t Z) {
+  return nimg >= 2 && nimg <= 64 && X >= 1 && Y >= 1 && Z >= 1 && X <= (1 << 15) && Y <= (1 << 15) &&
+         Z <= (1 << 15) && X * Y * Z < ((int64_t)1 << 31) - 2;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t hrf_register3_workspace_bytes(int32_t nimg, int64_t X, int64_t Y, int64_t Z) {
+  if (!sizes3_ok(nimg, X, Y, Z)) return -1;
+  const int64_t nc = X * Y * (Z / 2 + 1);
+  Plans p{};
+  {
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    if (get_plans3(X, Y, Z, &p) != HRF_OK) return -1;
+  }
+  return 2 * nc * (int64_t)sizeof(hipfftDoubleComplex) + X * Y * Z * (int64_t)sizeof(double) +
+         AM_BLOCKS * (int64_t)sizeof(Best) + 512 + (int64_t)p.work;
+}
+
+hrf_status hrf_register3_translations_dev(const double *vols, int32_t nimg, int64_t X, int64_t Y, int64_t Z,
+                                          void *work, int32_t clamp, int32_t *shifts_dev, hrf_stream_t stream) {
+  HRF_REQUIRE(sizes3_ok(nimg, X, Y, Z), "register3_translations: bad sizes");
+  HRF_REQUIRE(vols && work && shifts_dev, "register3_translations: null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nc = X * Y * (Z / 2 + 1), n = X * Y * Z;
+  hipfftDoubleComplex *fa = (hipfftDoubleComplex *)work;   // the reference's spectrum
+  hipfftDoubleComplex *fb = fa + nc;                       // a target's, then the product
+  double *cc = (double *)(fb + nc);
+  Best *part = (Best *)(cc + n);
+  char *fft_work = (char *)(((uintptr_t)(part + AM_BLOCKS) + 255) & ~(uintptr_t)255);
+  const unsigned nb = (unsigned)std::min<int64_t>(AM_BLOCKS, hrf::cdiv(n, 256));
+  for (int t = 1; t < nimg; ++t) {
+    {
+      std::lock_guard<std::mutex> lk(g_plan_mu);  // plan handles are shared; bind stream + work area, run
+      Plans p{};
+      if (hrf_status st = get_plans3(X, Y, Z, &p)) return st;
+      HRF_FFT(hipfftSetStream(p.fwd, s));
+      HRF_FFT(hipfftSetStream(p.inv, s));
+      HRF_FFT(hipfftSetWorkArea(p.fwd, fft_work));
+      HRF_FFT(hipfftSetWorkArea(p.inv, fft_work));
+      if (t == 1) HRF_FFT(hipfftExecD2Z(p.fwd, const_cast<double *>(vols), fa));
+      HRF_FFT(hipfftExecD2Z(p.fwd, const_cast<double *>(vols + (int64_t)t * n), fb));
+      xcorr_product_inplace_kernel<<<hrf::stream_grid(nc), 256, 0, s>>>(fa, nc, fb);
+      HRF_LAUNCHED();
+      HRF_FFT(hipfftExecZ2D(p.inv, fb, cc));  // unnormalised: a positive scale leaves the argmax
+    }
+    abs_argmax_partial_kernel<<<nb, 256, 0, s>>>(cc, n, part);
+    shift3_kernel<<<1, 256, 0, s>>>(part, (int)nb, X, Y, Z, clamp, shifts_dev + 3 * t, t == 1 ? shifts_dev : nullptr);
+    HRF_LAUNCHED();
+  }
+  return HRF_OK;
+}
 
 int64_t hrf_register_batch_workspace_bytes(int32_t nimg, int64_t H, int64_t W) {
   if (nimg < 2 || nimg > 64 || H < 1 || W < 1 || H > (1 << 15) || W > (1 << 15)) return -1;

@@ -32,6 +32,26 @@ def load_laser_stack(path: str) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def load_tstack(path: str) -> list:
+    """One laser's time series as the biofilm script reads it (hiprfish_imaging_biofilm_analysis.py
+    :135-141: load_image_zstack_fixed_t(filename, t) for t < get_t_range(filename)): a list of T
+    (H, W, Z, C) float32 z-stacks, ready for pipeline.t_average_volume once on the device.  When
+    only an array is at hand, {stem}.npy holds the (T, H, W, Z, C) array."""
+    stem, ext = os.path.splitext(path)
+    if ext.lower() == ".czi" and os.path.exists(path):
+        from . import czi
+        vols = [czi.load_image_zstack_fixed_t(path, t) for t in range(czi.get_t_range(path))]
+    else:
+        cand = path if ext == ".npy" else stem + ".npy"
+        if not os.path.exists(cand):
+            raise FileNotFoundError("%s: neither the CZI file nor %s exists" % (path, cand))
+        a = np.load(cand, allow_pickle=False)
+        if a.ndim != 5:
+            raise ValueError("%s: a (T, H, W, Z, C) array expected, got shape %s" % (cand, a.shape))
+        vols = list(a)
+    return [np.ascontiguousarray(v if v.ndim == 4 else v[..., None], dtype=np.float32) for v in vols]
+
+
 def sample_name_ecoli(first_image: str) -> str:
     """ecoli measurement.py:143  re.sub('_[0-9]*.czi', '', image_name[0])"""
     return re.sub('_[0-9]*.czi', '', first_image)

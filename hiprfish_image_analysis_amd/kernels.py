@@ -323,6 +323,140 @@ def xcorr_surfaces(imgs):
     return out
 
 
+def xcorr3_supported(n, X, Y, Z):
+    return int(_lib.lib().hrf_xcorr3_workspace_bytes(n, X, Y, Z)) > 0
+
+
+def _xcorr3_args(vols, where):
+    vols = _dev(vols, torch.float64, "vols")
+    if vols.dim() != 4:
+        raise ValueError("%s: an (n, X, Y, Z) tensor expected" % where)
+    n, X, Y, Z = vols.shape
+    nb = int(_lib.lib().hrf_xcorr3_workspace_bytes(n, X, Y, Z))
+    if nb <= 0:
+        raise ValueError("%s: unsupported size %d x %d x %d x %d" % (where, n, X, Y, Z))
+    return vols, torch.empty(nb, dtype=torch.uint8, device=vols.device)
+
+
+def xcorr3_shifts_dev(vols, clamp=None):
+    """register3_translations_dev(vols, clamp) through the hand-written FFT pipeline (xcorr.hip;
+    power-of-two sizes, xcorr3_supported) -> (n, 3) int32 device tensor"""
+    vols, work = _xcorr3_args(vols, "xcorr3_shifts")
+    n, X, Y, Z = vols.shape
+    out = torch.empty((n, 3), dtype=torch.int32, device=vols.device)
+    _lib.call("hrf_xcorr3_shifts_dev", _ptr(vols), n, X, Y, Z, _ptr(work), -1 if clamp is None else int(clamp),
+              _ptr(out), _stream())
+    return out
+
+
+def xcorr3_surfaces(vols):
+    """the cross-correlation surfaces of xcorr3_shifts_dev: (n - 1, X, Y, Z) f64, X * Y * Z / 2
+    times numpy.fft.ifftn(F(vols[0]) * conj(F(vols[t]))).real (tests)"""
+    vols, work = _xcorr3_args(vols, "xcorr3_surfaces")
+    n, X, Y, Z = vols.shape
+    out = torch.empty((n - 1, X, Y, Z), dtype=torch.float64, device=vols.device)
+    _lib.call("hrf_xcorr3_surfaces_dev", _ptr(vols), n, X, Y, Z, _ptr(work), _ptr(out), _stream())
+    return out
+
+
+def register3_translations_dev(vols, clamp=None):
+    """register_translation(vols[0], vols[t]) (upsample_factor 1) for t >= 1 on one (n, X, Y, Z)
+    f64 tensor (biofilm :143, :537) -> (n, 3) int32 device tensor of (sx, sy, sz), row 0 = 0.
+    hipFFT 3-D transforms, the reference's shared by every target; nothing synchronises."""
+    vols = _dev(vols, torch.float64, "vols")
+    if vols.dim() != 4 or vols.shape[0] < 2:
+        raise ValueError("register3_translations: an (n, X, Y, Z) tensor with n >= 2 expected")
+    n, X, Y, Z = vols.shape
+    nb = int(_lib.lib().hrf_register3_workspace_bytes(n, X, Y, Z))
+    if nb <= 0:
+        raise ValueError("register3_translations: unsupported size %d x %d x %d x %d" % (n, X, Y, Z))
+    work = torch.empty(nb, dtype=torch.uint8, device=vols.device)
+    out = torch.empty((n, 3), dtype=torch.int32, device=vols.device)
+    _lib.call("hrf_register3_translations_dev", _ptr(vols), n, X, Y, Z, _ptr(work), -1 if clamp is None else int(clamp),
+              _ptr(out), _stream())
+    return out
+
+
+_SUM_MODES = {None: None, "sum": 0, "log": 1}
+
+
+def _volumes(vols, name):
+    vols = [_dev(v, torch.float32, name) for v in vols]
+    if not vols or any(v.dim() != 4 or v.shape[:3] != vols[0].shape[:3] for v in vols):
+        raise ValueError("%s: (X, Y, Z, C) volumes of one X x Y x Z expected" % name)
+    return vols
+
+
+def _shifts3(shifts, n, device, name):
+    if isinstance(shifts, torch.Tensor) and shifts.is_cuda:
+        sd = _dev(shifts, torch.int32, "shifts")
+    else:
+        sd = torch.tensor([[int(v) for v in s] for s in shifts], dtype=torch.int32).reshape(-1, 3).to(device)
+    if tuple(sd.shape) != (n, 3):
+        raise ValueError("%s: one (sx, sy, sz) row per volume expected" % name)
+    return sd
+
+
+def volume_taverage(tstack, shifts, want_sum=None):
+    """biofilm :134-165 with the shifts given: tstack a list of T (X, Y, Z, C) f32 time points,
+    shifts (T, 3) int32 on the device (or host triples; row 0 is not read) ->
+    (tstack[0] + sum of the zero-filled shifted later time points) / T, added in f64 in t order,
+    stored f32.  want_sum "sum" / "log": also np.sum(out, axis=3) (numpy's order) / log(sum + 1e-8)
+    from the same pass -> (out, (X, Y, Z) f64)."""
+    import ctypes
+    tstack = _volumes(tstack, "volume_taverage")
+    if any(v.shape != tstack[0].shape for v in tstack):
+        raise ValueError("volume_taverage: the time points must share one shape")
+    X, Y, Z, C = tstack[0].shape
+    T = len(tstack)
+    sd = _shifts3(shifts, T, tstack[0].device, "volume_taverage") if T > 1 else None
+    mode = _SUM_MODES[want_sum]
+    ptrs = (ctypes.c_void_p * T)(*[v.data_ptr() for v in tstack])
+    out = torch.empty((X, Y, Z, C), dtype=torch.float32, device=tstack[0].device)
+    s = torch.empty((X, Y, Z), dtype=torch.float64, device=out.device) if mode is not None else None
+    _lib.call("hrf_volume_taverage_dev", ctypes.cast(ptrs, ctypes.c_void_p), T, _ptr(sd), X, Y, Z, C, _ptr(out),
+              _ptr(s), mode or 0, _stream())
+    return out if s is None else (out, s)
+
+
+def volume_assemble(lasers, shifts, fill="keep", want_sum=None):
+    """biofilm :536-558 (fill "keep") / :428-450 (fill "zero") with the shifts given: each
+    (X, Y, Z, C_l) f32 laser volume shifted by its row of shifts ((L, 3) int32 on the device, or
+    host triples) and concatenated on C.  want_sum as volume_taverage, over the concatenated row."""
+    import ctypes
+    if fill not in ("keep", "zero"):
+        raise ValueError("volume_assemble: fill must be 'keep' or 'zero'")
+    lasers = _volumes(lasers, "volume_assemble")
+    X, Y, Z = lasers[0].shape[:3]
+    L = len(lasers)
+    sd = _shifts3(shifts, L, lasers[0].device, "volume_assemble")
+    mode = _SUM_MODES[want_sum]
+    ch = _i32_host([v.shape[3] for v in lasers])
+    ptrs = (ctypes.c_void_p * L)(*[v.data_ptr() for v in lasers])
+    out = torch.empty((X, Y, Z, int(ch.sum())), dtype=torch.float32, device=lasers[0].device)
+    s = torch.empty((X, Y, Z), dtype=torch.float64, device=out.device) if mode is not None else None
+    _lib.call("hrf_volume_assemble_dev", ctypes.cast(ptrs, ctypes.c_void_p), ch.ctypes.data, _ptr(sd), L, X, Y, Z,
+              int(fill == "keep"), _ptr(out), _ptr(s), mode or 0, _stream())
+    return out if s is None else (out, s)
+
+
+def volume_channel_sum(vol, log=False, out=None):
+    """np.sum(vol, axis=3) of an (X, Y, Z, C) f32 volume in numpy's order (f64), C <= 128; log:
+    log(sum + 1e-8), the registration image of biofilm :537.  out: an (X, Y, Z) f64 tensor"""
+    import ctypes
+    vol = _volumes([vol], "volume_channel_sum")[0]
+    X, Y, Z, C = vol.shape
+    if out is None:
+        out = torch.empty((X, Y, Z), dtype=torch.float64, device=vol.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (X, Y, Z) or not out.is_contiguous():
+        raise ValueError("volume_channel_sum: out must be a contiguous (%d, %d, %d) f64 tensor" % (X, Y, Z))
+    ch = _i32_host([C])
+    ptrs = (ctypes.c_void_p * 1)(vol.data_ptr())
+    _lib.call("hrf_volume_assemble_dev", ctypes.cast(ptrs, ctypes.c_void_p), ch.ctypes.data, None, 1, X, Y, Z, 0,
+              None, _ptr(out), int(bool(log)), _stream())
+    return out
+
+
 def pad_edge_3d(a, width=5):
     """skimage.util.pad(a, width, mode='edge') of an (X, Y, Z) f64 volume (biofilm :810)"""
     a = _dev(a, torch.float64, "a")

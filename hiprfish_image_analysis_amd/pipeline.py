@@ -196,6 +196,85 @@ def register_tile(lasers, reduce: str = "max", clamp: int | None = 15, apply_mas
 
 
 # --------------------------------------------------------------------------------------------
+# Biofilm z-stack registration (hiprfish_imaging_biofilm_analysis.py:134-165, :532-559)
+# --------------------------------------------------------------------------------------------
+# Power-of-two volumes of at least XCORR3_MIN_VOXELS voxels: the registration cross-correlations
+# through xcorr.hip's 3-D pipeline instead of hipFFT (not slower in any alternating pair from
+# 256 x 256 x 32 up); HRF_XCORR3=0 keeps hipFFT, HRF_XCORR3=1 takes it at every size
+XCORR3 = os.environ.get("HRF_XCORR3", "")
+XCORR3_MIN_VOXELS = 1 << 21
+
+
+def estimate_shifts3(vols, clamp: int | None = None, xcorr: bool | None = None):
+    """skimage register_translation(vols[0], vols[t]) (upsample_factor 1) for every t >= 1 on an
+    (n, X, Y, Z) f64 tensor (or a list of (X, Y, Z) volumes) -> (n, 3) int32 device tensor of
+    (sx, sy, sz), row 0 = 0; |component| > clamp -> 0.  xcorr True / False picks the hand-written
+    pipeline (power-of-two sizes) / hipFFT; None: the hand-written one where the size is supported
+    and the volume has at least XCORR3_MIN_VOXELS voxels."""
+    if not isinstance(vols, torch.Tensor):
+        vols = torch.stack(list(vols))
+    if vols.shape[0] < 2:
+        return torch.zeros((vols.shape[0], 3), dtype=torch.int32, device=vols.device)
+    if xcorr is None:
+        big = vols[0].numel() >= XCORR3_MIN_VOXELS
+        xcorr = XCORR3 != "0" and (big or XCORR3 == "1") and K.xcorr3_supported(*vols.shape)
+    return K.xcorr3_shifts_dev(vols, clamp) if xcorr else K.register3_translations_dev(vols, clamp)
+
+
+def t_average_volume(tstack, want_shifts: bool = False, want_sum: str | None = None):
+    """biofilm :134-165, get_registered_average_image_from_tstack: tstack a list of T
+    (X, Y, Z, C) f32 time points of one laser.  Each is registered to t = 0 on the channel sums
+    (np.sum(axis=3), numpy's order; no log, no clamp), shifted with zero fill, added in f64 in t
+    order, divided by T and stored f32 -> (X, Y, Z, C) f32; T = 1 returns the time point's values.
+    want_shifts: also the (T, 3) device shifts; want_sum "sum" / "log": also np.sum(out, axis=3) /
+    log(sum + 1e-8) from the same pass.  Returns out, or (out[, shifts][, sum]).  One stream,
+    nothing synchronises."""
+    tstack = list(tstack)
+    T = len(tstack)
+    X, Y, Z, C = tstack[0].shape
+    sums = torch.empty((T, X, Y, Z), dtype=torch.float64, device=tstack[0].device)
+    if T > 1:
+        for i, a in enumerate(tstack):
+            K.channel_sum(a.reshape(X * Y, Z, C), out=sums[i].view(X * Y, Z))       # :137, :142
+    shifts = estimate_shifts3(sums)                                               # :143
+    res = K.volume_taverage(tstack, shifts, want_sum)                             # :144-165
+    out, s = res if want_sum else (res, None)
+    ret = (out,) + ((shifts,) if want_shifts else ()) + ((s,) if want_sum else ())
+    return ret[0] if len(ret) == 1 else ret
+
+
+def register_volume(lasers, fill: str = "keep", shifts=None, want_sum: bool = False, log_sums=None):
+    """biofilm :536-558 (fill "keep", get_t_average_image) or :426-450 (fill "zero"): the averaged
+    lasers, (X, Y, Z, C_l) f32 each, registered to the first on log(channel sum + 1e-8) (no clamp),
+    shifted and concatenated on C -> (X, Y, Z, sum C_l) f32.  shifts: an (L, 3) device tensor or host
+    triples to use instead of the estimate; log_sums: the (L, X, Y, Z) f64 registration images when
+    already computed (t_average_volume(want_sum="log")); want_sum: also np.sum(out, axis=3) from
+    the assembly pass -> (out, sum).  One stream, nothing synchronises."""
+    lasers = list(lasers)
+    if shifts is None:
+        if log_sums is None:
+            X, Y, Z = lasers[0].shape[:3]
+            log_sums = torch.empty((len(lasers), X, Y, Z), dtype=torch.float64, device=lasers[0].device)
+            for i, v in enumerate(lasers):
+                K.volume_channel_sum(v, log=True, out=log_sums[i])                 # :536-537
+        shifts = estimate_shifts3(log_sums)                                       # :537-538
+    return K.volume_assemble(lasers, shifts, fill, "sum" if want_sum else None)   # :539-558
+
+
+def register_volume_tstacks(tstacks, fill: str = "keep", want_sum: bool = False):
+    """biofilm :532-559, get_t_average_image from raw acquisitions: tstacks[l] the list of time
+    points of laser l.  Each laser is t-averaged (t_average_volume), the averages are registered and
+    concatenated (register_volume) -> the registered (X, Y, Z, sum C_l) f32 stack (with want_sum
+    also its channel sum, for segment_volume_stack(stack_sum=...))."""
+    avg, logs = [], []
+    for ts in tstacks:
+        a, s = t_average_volume(ts, want_sum="log")
+        avg.append(a)
+        logs.append(s)
+    return register_volume(avg, fill, want_sum=want_sum, log_sums=torch.stack(logs))
+
+
+# --------------------------------------------------------------------------------------------
 # Biofilm 3-D enhancement input (hiprfish_imaging_biofilm_analysis.py:808-817)
 # --------------------------------------------------------------------------------------------
 def enhance_volume(stack: torch.Tensor, v3: bool = False) -> torch.Tensor:
@@ -205,11 +284,17 @@ def enhance_volume(stack: torch.Tensor, v3: bool = False) -> torch.Tensor:
     return _enhance_norm(volume_sum_norm(stack), v3)
 
 
-def volume_sum_norm(stack: torch.Tensor) -> torch.Tensor:
+def volume_sum_norm(stack: torch.Tensor, stack_sum: torch.Tensor | None = None) -> torch.Tensor:
     """biofilm :808-809: the channel sum of the registered (X, Y, Z, C) volume (numpy order) over
-    its maximum -> image_registered_sum (X, Y, Z) f64"""
+    its maximum -> image_registered_sum (X, Y, Z) f64.  stack_sum: np.sum(stack, axis=3) when the
+    registration already wrote it (register_volume(want_sum=True)); the stack is then not read"""
     X, Y, Z, C = stack.shape
-    s = K.channel_sum(stack.reshape(X * Y, Z, C)).reshape(X, Y, Z)     # :808
+    if stack_sum is not None:
+        s = K._dev(stack_sum, torch.float64, "stack_sum")
+        if tuple(s.shape) != (X, Y, Z):
+            raise ValueError("volume_sum_norm: stack_sum must be the (X, Y, Z) channel sum of the stack")
+    else:
+        s = K.channel_sum(stack.reshape(X * Y, Z, C)).reshape(X, Y, Z)     # :808
     return K.div_scalar(s, K.max_f64(s))                                # :809
 
 
@@ -274,10 +359,12 @@ def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None
     return out
 
 
-def segment_volume_stack(stack: torch.Tensor, keep: dict | None = None, adjacency: bool = False, v3: bool = False):
+def segment_volume_stack(stack: torch.Tensor, keep: dict | None = None, adjacency: bool = False, v3: bool = False,
+                         stack_sum: torch.Tensor | None = None):
     """biofilm :808-859 from the registered (X, Y, Z, C) volume: enhance_volume, then
-    segment_volume on image_final and the normalised sum it was made from"""
-    s = volume_sum_norm(stack)
+    segment_volume on image_final and the normalised sum it was made from.  stack_sum: the stack's
+    channel sum when register_volume(want_sum=True) already wrote it"""
+    s = volume_sum_norm(stack, stack_sum)
     final = _enhance_norm(s, v3)
     if keep is not None:
         keep.update(reg_sum=s, final=final)

@@ -189,6 +189,21 @@ HRF_API hrf_status hrf_xcorr_shifts_dev(const double *imgs, int32_t nimg, int64_
 HRF_API hrf_status hrf_xcorr_surfaces_dev(const double *imgs, int32_t nimg, int64_t H, int64_t W, void *work,
                                           double *cc_out, hrf_stream_t stream);
 
+/* the same pipeline on volumes (xcorr3.hip; biofilm :143, :537): vols nimg x X x Y x Z f64, Z contiguous
+ * (reference first).  Z-lines as batched real FFTs (several lines per workgroup), the y axis as
+ * four-step passes whose permuted order their own inverse undoes, the x axis through the 2-D
+ * column passes on the (X, Y (Z/2+1)) matrix, the first maximum of |cc| in C order.
+ * X, Y powers of two 16..4096, Z 4..2048, X Y Z < 2^31 - 2, nimg 2..16.  work:
+ * hrf_xcorr3_workspace_bytes device bytes, one spectrum per volume (-1: size unsupported -- use
+ * hrf_register3_translations_dev); shifts_dev: nimg x 3 int32 (sx, sy, sz), row 0 = 0; clamp as
+ * above.  cc_out: (nimg - 1) x X x Y x Z f64 = X * Y * Z / 2 * numpy.fft.ifftn(F(ref)
+ * conj(F(vol_t))).real.  Stream-ordered, no synchronisation. */
+HRF_API int64_t hrf_xcorr3_workspace_bytes(int32_t nimg, int64_t X, int64_t Y, int64_t Z);
+HRF_API hrf_status hrf_xcorr3_shifts_dev(const double *vols, int32_t nimg, int64_t X, int64_t Y, int64_t Z,
+                                         void *work, int32_t clamp, int32_t *shifts_dev, hrf_stream_t stream);
+HRF_API hrf_status hrf_xcorr3_surfaces_dev(const double *vols, int32_t nimg, int64_t X, int64_t Y, int64_t Z,
+                                           void *work, double *cc_out, hrf_stream_t stream);
+
 /* ==== f1: registration shift estimate (register.hip) ====================================
  * skimage.feature.register_translation(src, target)[0] (upsample_factor 1; ecoli :45-46,
  * multispecies :82-83): argmax |ifft(F(src) conj(F(target)))| wrapped to (-n/2, n/2] per
@@ -209,6 +224,41 @@ HRF_API int64_t hrf_register_batch_workspace_bytes(int32_t nimg, int64_t H, int6
 HRF_API hrf_status hrf_register_translations_batch_dev(const double *imgs, int32_t nimg, int64_t H, int64_t W,
                                                        void *work, int32_t clamp, int32_t *shifts_dev,
                                                        hrf_stream_t stream);
+/* register_translation on volumes (biofilm :143, :537): vols = nimg contiguous (X, Y, Z) f64
+ * volumes, reference first; shifts_dev = nimg x 3 int32 (sx, sy, sz), row 0 = 0.  hipFFT 3-D
+ * D2Z / Z2D (plans cached per device and size), the reference's transform shared by every target,
+ * first maximum of |cc| in C order, wrapped per axis (k > fix(n / 2) -> k - n); clamp as above.
+ * 2 <= nimg <= 64, every axis 1..32768, X Y Z < 2^31 - 2.  work:
+ * hrf_register3_workspace_bytes(nimg, X, Y, Z) device bytes (-1: bad sizes).  Stream-ordered. */
+HRF_API int64_t hrf_register3_workspace_bytes(int32_t nimg, int64_t X, int64_t Y, int64_t Z);
+HRF_API hrf_status hrf_register3_translations_dev(const double *vols, int32_t nimg, int64_t X, int64_t Y, int64_t Z,
+                                                  void *work, int32_t clamp, int32_t *shifts_dev,
+                                                  hrf_stream_t stream);
+
+/* ==== registered biofilm z-stacks (volreg.hip) ============================================
+ * Shift s on an axis of length n: dst[max(0,s) : n+min(0,s)] = src[-min(0,s) : n-max(0,s)].
+ * Volumes are (X, Y, Z, C) f32, X Y Z < 2^31 - 2 (X Y Z C may pass 2^31: 64-bit element
+ * indices), at most 128 channels in an output row, at most 16 sources.  Shifts are read from
+ * DEVICE memory, (sx, sy, sz) int32 per source.  sum_out (nullable, X Y Z f64): np.sum(dst,
+ * axis=3) in numpy's pairwise order from the same pass, sum_mode 0 raw, 1 log(sum + 1e-8) (:537).
+ * dst must not alias a source.  Stream-ordered, no synchronisation.
+ *
+ * hrf_volume_taverage_dev (:134-165): src_host[t], t < T, the time points of one laser;
+ * dst = (src[0] + sum_{t >= 1} shift_zero(src[t], shifts_dev[3t..3t+2])) / T, added in f64 in t
+ * order, stored f32 (round to nearest).  Row 0 of shifts_dev is not read; T = 1: shifts_dev may
+ * be NULL and dst = src[0]. */
+HRF_API hrf_status hrf_volume_taverage_dev(const float *const *src_host, int32_t T, const int32_t *shifts_dev,
+                                           int64_t X, int64_t Y, int64_t Z, int32_t C, float *dst, double *sum_out,
+                                           int32_t sum_mode, hrf_stream_t stream);
+/* hrf_volume_assemble_dev (:536-558 fill 1, :428-450 fill 0): nlaser volumes of channels_host[l]
+ * channels, each shifted by its own row of shifts_dev, concatenated on C into dst.  fill 0: zero
+ * outside the shifted box; fill 1 (keep): the unshifted source there (the reference assigns a
+ * volume onto itself; numpy copies the overlapping source first).  shifts_dev NULL: no shift;
+ * dst NULL (with sum_out): only the channel sum is written. */
+HRF_API hrf_status hrf_volume_assemble_dev(const float *const *src_host, const int32_t *channels_host,
+                                           const int32_t *shifts_dev, int32_t nlaser, int64_t X, int64_t Y, int64_t Z,
+                                           int32_t fill, float *dst, double *sum_out, int32_t sum_mode,
+                                           hrf_stream_t stream);
 
 /* ==== a4: non-local means (nlmeans.hip) ==================================================
  * skimage.restoration.denoise_nl_means(img, patch_size, patch_distance, h, fast_mode=True,
