@@ -21,7 +21,7 @@ _CT = {
     "const int32_t *": ctypes.c_void_p, "int32_t *": ctypes.c_void_p,
     "const int64_t *": ctypes.c_void_p, "int64_t *": ctypes.c_void_p,
     "const uint8_t *": ctypes.c_void_p, "uint8_t *": ctypes.c_void_p,
-    "const int16_t *": ctypes.c_void_p, "int16_t *": ctypes.c_void_p,
+    "const int16_t *": ctypes.c_void_p, "int16_t *": ctypes.c_void_p, "uint64_t *": ctypes.c_void_p,
     "void *": ctypes.c_void_p, "const void *": ctypes.c_void_p,
     "hrf_stream_t": ctypes.c_void_p, "size_t": ctypes.c_size_t,
     "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "double": ctypes.c_double,

@@ -1384,6 +1384,86 @@ def cell_typing(label, area, maxprob=None, overlap=None, maxlab=0, area_max=1000
     return out
 
 
+# ---- the 3-D per-cell report (report3.hip) ----------------------------------------------------
+def region_moments3(labels, maxlab):
+    """the exact voxel moments of every label 1..maxlab of an (X, Y, Z) volume as a (maxlab + 1, 4)
+    int64 table: count, sum x, sum y, sum z (row 0 and labels outside 1..maxlab: zero)"""
+    l = _i32(labels, "labels")
+    X, Y, Z = _xyz(l, "region_moments3")
+    mom = torch.empty((maxlab + 1, 4), dtype=torch.int64, device=l.device)
+    _lib.call("hrf_region_moments3", _ptr(l), X, Y, Z, maxlab, _ptr(mom), _stream())
+    return mom
+
+
+def region_props3(labels, maxlab):
+    """the regionprops fields the 3-D report reads (biofilm :1382-1386) as a (maxlab + 1, 5) f64
+    table: area, centroid x, y, z (the exact sum over the count), valid flag"""
+    mom = region_moments3(labels, maxlab)
+    props = torch.empty((maxlab + 1, 5), dtype=torch.float64, device=mom.device)
+    _lib.call("hrf_region_props3", _ptr(mom), maxlab, _ptr(props), _stream())
+    return props
+
+
+def rag_edges3(labels, conn=2, capacity=None, attempts: list | None = None):
+    """skimage.future.graph.rag_boundary's edge set on an (X, Y, Z) label volume as a sorted int64
+    tensor of keys (a << 32) | b, a < b (conn 1, 2, 3: the 7-, 19-, 27-point footprint; background
+    pairs, a = 0, included).  The device set has `capacity` slots (a power of two; default the
+    next one >= 32 * (max label + 1)) and is rebuilt with four times as many whenever it overflows,
+    so the result does not depend on it.  attempts (optional list) receives (capacity, keys stored,
+    overflow flag) per build.  Synchronises per build."""
+    l = _i32(labels, "labels")
+    X, Y, Z = _xyz(l, "rag_edges3")
+    if capacity is None:
+        top = max(int(l.max().item()), 0) if l.numel() else 0
+        capacity = 1 << (32 * (top + 1) - 1).bit_length()
+    cap = int(capacity)
+    if cap < 2 or cap & (cap - 1):
+        raise ValueError("rag_edges3: capacity must be a power of two >= 2")
+    while True:
+        table = torch.empty(cap, dtype=torch.int64, device=l.device)
+        info = torch.empty(2, dtype=torch.int32, device=l.device)
+        _lib.call("hrf_rag_edges3", _ptr(l), X, Y, Z, int(conn), _ptr(table), cap, _ptr(info), _stream())
+        count, overflow = (int(v) for v in info.cpu())
+        if attempts is not None:
+            attempts.append((cap, count, overflow))
+        if not overflow:
+            break
+        del table
+        cap *= 4
+    return torch.sort(table[table != -1]).values
+
+
+def barcode_adjacency_edges(keys, bc_of_label, R, keep_of_label=None):
+    """barcode x barcode counts (biofilm :1283-1295) over the keys of rag_edges3 -> (R, R) int64, or
+    (raw, cell-filtered) with keep_of_label: every key with 1 <= a < b <= max label and both barcodes
+    in 0..R-1 counts at [ba][bb] and [bb][ba]; bc_of_label / keep_of_label hold max label + 1 entries"""
+    k = _dev(keys, torch.int64, "keys")
+    bc = _i32(bc_of_label, "bc_of_label")
+    keep = None if keep_of_label is None else _u8(keep_of_label, "keep_of_label")
+    maxlab = bc.numel() - 1
+    if maxlab < 0 or (keep is not None and keep.numel() != bc.numel()):
+        raise ValueError("barcode_adjacency_edges: per-label arrays must hold max label + 1 entries")
+    adj = torch.empty((R, R), dtype=torch.int64, device=k.device)
+    adjf = None if keep is None else torch.empty((R, R), dtype=torch.int64, device=k.device)
+    _lib.call("hrf_barcode_adjacency_edges", _ptr(k), k.numel(), _ptr(bc), _ptr(keep), maxlab, R, _ptr(adj),
+              _ptr(adjf), _stream())
+    return adj if keep is None else (adj, adjf)
+
+
+def paint_planes3(labels, colour):
+    """the identification volume as Blender voxel planes (biofilm :285-288): (3, Z, Y, X) f32 with
+    [ch, z, y, x] = colour[labels[x, y, z], ch]; colour (ncell + 1, 3) f32, row 0 the background,
+    which labels outside 0..ncell also get.  planes[ch] is image[:, :, :, ch].flatten('F')."""
+    l = _i32(labels, "labels")
+    X, Y, Z = _xyz(l, "paint_planes3")
+    c = _dev(colour, torch.float32, "colour")
+    if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < 1:
+        raise ValueError("paint_planes3: colour must be (ncell + 1, 3)")
+    planes = torch.empty((3, Z, Y, X), dtype=torch.float32, device=l.device)
+    _lib.call("hrf_paint_planes3", _ptr(l), X, Y, Z, _ptr(c), c.shape[0] - 1, _ptr(planes), _stream())
+    return planes
+
+
 def shape_filter(labels, props, maxlab, minor_lo=15.0, minor_hi=35.0):
     l = _i32(labels, "labels")
     H, W = l.shape

@@ -740,3 +740,32 @@ def biofilm_typing_and_adjacency(segmentation: torch.Tensor, adjacency_seg: torc
     adj, adjf = K.barcode_adjacency_filtered(edge, bc, keep, R)                       # :1283-1295
     return CellTyping(is_cell, overlap if overlap is not None else torch.zeros(maxlab + 1, dtype=torch.uint8,
                                                                               device=seg.device), adj, adjf)
+
+
+def biofilm_typing_and_adjacency3(segmentation: torch.Tensor, adjacency_seg: torch.Tensor, bc_idx: torch.Tensor,
+                                  R: int, max_probability: torch.Tensor | None = None, area_max: float = 100000.0,
+                                  prob_min: float = 0.95, conn: int = 2) -> CellTyping:
+    """biofilm_typing_and_adjacency on (X, Y, Z) volumes (measure_biofilm_images_3d, :1359-1417):
+    rows = the labels of `segmentation` ascending, row i standing for node i + 1 of the adjacency
+    graph of `adjacency_seg`.  The 3-D rule is :1411 -- debris when area > 100000 or max_probability
+    <= 0.95; its loop never consults debris_labels (image_epithelial_area is not defined there), so
+    debris_labels comes back all zero.  The graph is rag_boundary's with its default connectivity 2
+    (conn), held as a sparse edge set: no label limit."""
+    seg = segmentation.to(torch.int32).contiguous()
+    maxlab = int(seg.max().item()) if seg.numel() else 0
+    props = K.region_props3(seg, maxlab)
+    present = props[1:, 4] > 0
+    labels = (torch.nonzero(present).flatten() + 1).to(torch.int32)
+    area = props[1:, 0][present].contiguous()
+    is_cell = K.cell_typing(labels, area, max_probability, None, maxlab, area_max, prob_min)      # :1411
+    aseg = adjacency_seg.to(torch.int32).contiguous()
+    amax = max(int(aseg.max().item()), 0) if aseg.numel() else 0
+    keys = K.rag_edges3(aseg, conn)
+    n = labels.numel()
+    bc = torch.full((amax + 1,), -1, dtype=torch.int32, device=seg.device)
+    keep = torch.zeros(amax + 1, dtype=torch.uint8, device=seg.device)
+    m = min(n, amax)
+    bc[1:m + 1] = bc_idx[:m].to(torch.int32)
+    keep[1:m + 1] = is_cell[:m]
+    adj, adjf = K.barcode_adjacency_edges(keys, bc, R, keep)
+    return CellTyping(is_cell, torch.zeros(maxlab + 1, dtype=torch.uint8, device=seg.device), adj, adjf)

@@ -724,6 +724,39 @@ HRF_API hrf_status hrf_cell_typing(const int32_t *label, const double *area, con
                                    const uint8_t *overlap, int32_t maxlab, int64_t n, double area_max, double prob_min,
                                    uint8_t *is_cell, hrf_stream_t stream);
 
+/* ==== the 3-D per-cell report (report3.hip) ================================================
+ * biofilm :1359-1417 (measure_biofilm_images_3d) and :280-289 (save_identification_bvox).
+ * Volumes are (X, Y, Z) int32 labels, Z fastest, X * Y * Z < 2^31 - 2 (HRF_EINVAL above). */
+/* exact voxel moments mom[(maxlab+1)*4] = {count, sum x, sum y, sum z} of every label 1..maxlab;
+ * row 0 and labels outside 1..maxlab: zero */
+HRF_API hrf_status hrf_region_moments3(const int32_t *labels, int64_t X, int64_t Y, int64_t Z, int32_t maxlab,
+                                       int64_t *mom, hrf_stream_t stream);
+/* the regionprops fields the 3-D report reads (:1382-1386): props[(maxlab+1)*5] = {area, centroid
+ * x, y, z, valid}, a centroid being the exact sum divided once by the count; an absent label: zeros */
+HRF_API hrf_status hrf_region_props3(const int64_t *mom, int32_t maxlab, double *props, hrf_stream_t stream);
+/* skimage.future.graph.rag_boundary's edge set on a volume: per voxel v the pairs (min over the
+ * footprint, v) and (v, max over the footprint) where they differ from v; conn 1, 2, 3 = the 7-,
+ * 19-, 27-point footprint of scipy.ndimage.generate_binary_structure(3, conn) (2: rag_boundary's
+ * default).  table: an open-addressing set of cap (a power of two) keys (a << 32) | b, a < b, the
+ * empty slot all ones; pairs with a = 0 (background) are kept, a pair with a negative member is
+ * not.  info_dev[0] = distinct keys stored, info_dev[1] = 1 when a probe sequence ran through the
+ * whole table (keys are then missing: call again with a larger one).  Clears table and info_dev
+ * itself; stream-ordered, no synchronisation. */
+HRF_API hrf_status hrf_rag_edges3(const int32_t *labels, int64_t X, int64_t Y, int64_t Z, int32_t conn,
+                                  uint64_t *table, int64_t cap, int32_t *info_dev, hrf_stream_t stream);
+/* hrf_barcode_adjacency_filtered's rule over E keys of such a set (any order; an empty slot's all
+ * ones is skipped): every key with 1 <= a < b <= maxlab and both barcodes in 0..R-1 adds 1 at
+ * [ba][bb] and at [bb][ba], in adj_filtered (nullable; needs keep_of_label) only when both keep
+ * flags are set.  bc_of_label, keep_of_label: maxlab + 1 entries.  No label limit besides int32. */
+HRF_API hrf_status hrf_barcode_adjacency_edges(const int64_t *keys, int64_t E, const int32_t *bc_of_label,
+                                               const uint8_t *keep_of_label, int32_t maxlab, int32_t R, int64_t *adj,
+                                               int64_t *adj_filtered, hrf_stream_t stream);
+/* the identification volume as Blender voxel planes (:285-288, image_identification[:,:,:,ch]
+ * .flatten('F').astype('<f4')): planes[ch][(z * Y + y) * X + x] = colour[label(x, y, z)][ch], ch < 3;
+ * colour (ncell + 1) x 3 f32, row 0 the background, which labels outside 0..ncell also get */
+HRF_API hrf_status hrf_paint_planes3(const int32_t *labels, int64_t X, int64_t Y, int64_t Z, const float *colour,
+                                     int32_t ncell, float *planes, hrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
