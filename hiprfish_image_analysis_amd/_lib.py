@@ -60,6 +60,10 @@ class HrfError(RuntimeError):
     pass
 
 
+class HrfValueError(HrfError, ValueError):
+    """HRF_EINVAL: the library refused an argument (a ValueError, as it always was, and an HrfError)"""
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -84,6 +88,6 @@ def call(name, *args):
     if st != 0:
         msg = L.hrf_last_error().decode(errors="replace")
         if st == 1:
-            raise ValueError("%s: %s" % (name, msg))
+            raise HrfValueError("%s: %s" % (name, msg))
         raise HrfError("%s failed (status %d): %s" % (name, st, msg))
     return st

@@ -19,6 +19,10 @@ The identification images (:1247-1258, :1260-1270: colour renderings) are not wr
 The reference's script does not run as shipped (SyntaxError at :1254-1255), so
 the layouts follow its source text.
 
+measure_biofilm_2d is the whole 2-D mode (:1208-1295) from the acquisitions: registration and
+segmentation (generate_2d_segmentation, :322-419) on the device, the four arrays of :1210-1213, then
+cell_report.
+
 volume_report is the same report for a segmented z-stack (measure_biofilm_images_3d, :1359-1417):
 centroid_x/y/z and area for the shape columns, the sparse 3-D label adjacency, the barcode-valued
 identification volumes and the Blender voxel files {sample}_identification[_filtered]_{r,g,b}.bvox
@@ -100,6 +104,39 @@ def cell_report(sample: str, registered: torch.Tensor, segmentation: torch.Tenso
         out["avgint_filtered"].to_csv("{}_avgint_filtered.csv".format(sample), index=None)
         out["adjacency"].to_csv(sample + "_adjacency_matrix.csv")                         # :1294
         out["adjacency_filtered"].to_csv(sample + "_adjacency_matrix_filtered.csv")       # :1295
+    return out
+
+
+def measure_biofilm_2d(sample: str, lasers, model, taxon_codes, write: bool = True, **seg_kwargs):
+    """measure_biofilm_images_2d (:1208-1295) from the acquisitions of one field of view: register
+    (pipeline.register_biofilm_2d, :323-346), segment (pipeline.segment_biofilm_2d, :347-418), save
+    the reference's four arrays (:1210-1213)
+
+      {sample}_registered.npy        (H, W, C) registered stack, f64 as np.zeros(image.shape) makes it
+      {sample}_seg.npy               segmentation
+      {sample}_adjacency_seg.npy     adjacency segmentation
+      {sample}_epithelial_area.npy   bool
+
+    and report per cell with cell_report and the epithelial area.  seg_kwargs go to
+    segment_biofilm_2d (disk_radius, bkg_min_size, keep); epithelial=False is refused, the report
+    needs the area.  `lasers`: the (H, W, C_l) f32 device stacks in acquisition order.
+    -> cell_report's dict plus registered, segmentation, adjacency_seg, epithelial_area,
+    image_registered_sum and image_final_bkg_filtered (device tensors).
+
+    There is no command-line main: the reference's (:1419-1449) builds its taxon lookup from NCBI
+    over the network (:1429); the caller passes `taxon_codes` instead."""
+    if not seg_kwargs.get("epithelial", True):
+        raise ValueError("measure_biofilm_2d: the report needs the epithelial area")
+    registered = P.register_biofilm_2d(lasers)
+    seg, n, adj, n_adj, reg_sum, final_bkg, epi = P.segment_biofilm_2d(registered, **seg_kwargs)
+    if write:
+        np.save("{}_registered.npy".format(sample), registered.cpu().numpy().astype(np.float64))   # :1210
+        np.save("{}_seg.npy".format(sample), seg.cpu().numpy())                          # :1211
+        np.save("{}_adjacency_seg.npy".format(sample), adj.cpu().numpy())                # :1212
+        np.save("{}_epithelial_area.npy".format(sample), epi.cpu().numpy().astype(bool))  # :1213
+    out = cell_report(sample, registered, seg, adj, model, taxon_codes, epithelial_area=epi, write=write)
+    out.update(registered=registered, segmentation=seg, adjacency_seg=adj, epithelial_area=epi,
+               image_registered_sum=reg_sum, image_final_bkg_filtered=final_bkg)
     return out
 
 

@@ -836,6 +836,92 @@ def log10p1(x):
     return out
 
 
+# ---- 2-D biofilm segmentation stages (biofilm2d.hip) ----------------------------------------
+def _disk_args(mask, radius, name):
+    m = _u8(mask, "mask")
+    if m.dim() != 2:
+        raise ValueError("%s: a 2-D mask expected, got shape %s" % (name, tuple(m.shape)))
+    H, W = (int(d) for d in m.shape)
+    nb = int(_lib.lib().hrf_disk_workspace_bytes(H, W, int(radius)))
+    if nb <= 0:
+        raise _lib.HrfValueError("%s: radius %d outside 1..1023 or a %d x %d image too large"
+                                 % (name, int(radius), H, W))
+    return m, H, W, nb
+
+
+def binary_dilation_disk(mask, radius, work=None):
+    """skimage.morphology.binary_dilation(mask, disk(radius)) (biofilm :413): a pixel is set iff a set
+    pixel of the image lies within `radius` of it, 1 <= radius <= 1023.  work: a device uint8 tensor
+    of at least hrf_disk_workspace_bytes(H, W, radius) bytes to use instead of a fresh one"""
+    m, H, W, nb = _disk_args(mask, radius, "binary_dilation_disk")
+    ws = torch.empty(nb, dtype=torch.uint8, device=m.device) if work is None else _dev(work, torch.uint8, "work")
+    out = torch.empty_like(m)
+    _lib.call("hrf_binary_dilation_disk", _ptr(m), H, W, int(radius), _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def binary_erosion_disk(mask, radius, border_value=1, work=None):
+    """binary erosion by disk(radius); border_value 1 is skimage.morphology.binary_erosion's (pixels
+    outside the image do not erode), 0 scipy.ndimage's default"""
+    m, H, W, nb = _disk_args(mask, radius, "binary_erosion_disk")
+    ws = torch.empty(nb, dtype=torch.uint8, device=m.device) if work is None else _dev(work, torch.uint8, "work")
+    out = torch.empty_like(m)
+    _lib.call("hrf_binary_erosion_disk", _ptr(m), H, W, int(radius), int(border_value), _ptr(out), _ptr(ws),
+              ws.numel(), _stream())
+    return out
+
+
+def binary_closing_disk(mask, radius):
+    """skimage.morphology.binary_closing(mask, disk(radius)) (biofilm :408): the dilation, then the
+    erosion with border value 1, on one workspace"""
+    m, H, W, nb = _disk_args(mask, radius, "binary_closing_disk")
+    ws = torch.empty(nb, dtype=torch.uint8, device=m.device)
+    return binary_erosion_disk(binary_dilation_disk(m, radius, work=ws), radius, 1, work=ws)
+
+
+def log10(x):
+    """np.log10(x) on f64 with the correctly rounded log10 (biofilm :383)"""
+    x = _dev(x, torch.float64, "x")
+    out = torch.empty_like(x)
+    _lib.call("hrf_log10_f64", _ptr(x), x.numel(), _ptr(out), _stream())
+    return out
+
+
+def log(x):
+    """np.log(x) on f64 with the correctly rounded log (biofilm :327)"""
+    x = _dev(x, torch.float64, "x")
+    out = torch.empty_like(x)
+    _lib.call("hrf_log_f64", _ptr(x), x.numel(), _ptr(out), _stream())
+    return out
+
+
+def cluster_positive_means(labels, values, k):
+    """per cluster id 0..k-1 the sum and the count of values[labels == id] that are > 0 (biofilm
+    :385-388) -> (sums f64[k], counts i64[k]) on the device, the same bits on every run"""
+    l = _i32(labels, "labels")
+    v = _dev(values, torch.float64, "values")
+    if l.numel() != v.numel():
+        raise ValueError("cluster_positive_means: labels and values differ in size")
+    sums = torch.empty(k, dtype=torch.float64, device=v.device)
+    counts = torch.empty(k, dtype=torch.int64, device=v.device)
+    _lib.call("hrf_cluster_positive_means", _ptr(l), _ptr(v), v.numel(), int(k), _ptr(sums), _ptr(counts), _stream())
+    return sums, counts
+
+
+def largest_label(labels, maxlab, sync=True):
+    """the label in 1..maxlab with the most pixels, the lowest among equals, and its area: np.argmax
+    over regionprops areas (biofilm :411-412, :417-418); label 0 when none occurs
+    -> (label, area), or the (2,) int32 device tensor with sync=False"""
+    l = _i32(labels, "labels")
+    out = torch.empty(2, dtype=torch.int32, device=l.device)
+    work = torch.empty(int(maxlab) + 1, dtype=torch.int32, device=l.device)
+    _lib.call("hrf_largest_label", _ptr(l), l.numel(), int(maxlab), _ptr(out), _ptr(work), _stream())
+    if sync:
+        lab, area = out.tolist()
+        return lab, area
+    return out
+
+
 def watershed3(image, markers, mask=None, negate=False, ties: list | None = None, max_passes=100000):
     """skimage.morphology.watershed(+/-image, markers, mask=mask) on an (X, Y, Z) volume,
     connectivity 1.  `ties` (a list) receives [contested voxels, 1 if the serial heap flood ran,

@@ -108,7 +108,9 @@ def estimate_shifts(lasers, reduce: str = "max", clamp: int | None = 15, device:
     """Integer shift of every laser stack against the first, skimage register_translation
     (upsample 1) on a per-laser projection:
     * reduce "max": np.max(image, axis=2), |shift| > clamp -> 0 (ecoli measurement.py:45-57);
-    * reduce "sum": np.sum(image, axis=2), no clamp (multispecies measurement.py:82-84).
+    * reduce "sum": np.sum(image, axis=2), no clamp (multispecies measurement.py:82-84);
+    * reduce "logsum": np.log(np.sum(image, axis=2)), the correctly rounded log with no epsilon
+      (biofilm :326-327; every channel sum must be positive).
     -> [(0, 0), (dr_1, dc_1), ...] ready for kernels.register_assemble; with `device` an
     (nlaser, 2) int32 device tensor instead (no host synchronisation; register_assemble reads
     it on the device)."""
@@ -123,6 +125,8 @@ def estimate_shifts(lasers, reduce: str = "max", clamp: int | None = 15, device:
         for i, s in enumerate(lasers):
             K.channel_sum(s, out=proj[i])                               # numpy's pairwise order
         return K.xcorr_shifts_dev(proj, clamp)
+    elif reduce == "logsum":
+        proj = [K.log(K.channel_sum(s)) for s in lasers]                # biofilm :326-327
     else:
         proj = [K.channel_max(s) if reduce == "max" else K.channel_sum(s) for s in lasers]
     if device:
@@ -378,6 +382,119 @@ def measure_volume(stack: torch.Tensor, seg: torch.Tensor, n: int):
     sums, counts = K.label_sums(stack.reshape(X * Y, Z, C), seg.reshape(X * Y, Z), n)
     _, lor, avgint, avgint_norm = K.cell_table(sums, counts, n)
     return Measurement(seg, n, lor, avgint, avgint_norm)
+
+
+# --------------------------------------------------------------------------------------------
+# Biofilm 2-D registration and segmentation (hiprfish_imaging_biofilm_analysis.py:322-419)
+# --------------------------------------------------------------------------------------------
+def register_biofilm_2d(lasers, shifts=None):
+    """biofilm :323-346: the acquisitions (488, 514, 561, 633) registered against the first on
+    log(channel sum) -- skimage register_translation(log(sum_0), log(sum_i)), the correctly rounded
+    log, no clamp and no epsilon (:326-327) -- and concatenated with zeros outside each shifted
+    frame; the coverage mask is built but never applied (:345), as in register_multispecies.
+    shifts: (n, 2) device tensor or host pairs to use instead of the estimate.
+    -> (H, W, C) f32 registered stack (one stream, no synchronisation)
+
+    The reference takes shape[0] for both axes (:331), so it is right for square images only; here
+    every laser is shifted inside its own (H, W) frame, H != W included.
+    Precondition, not checked: every channel sum is positive (a zero gives log -inf, and the
+    reference's FFT then yields NaN shifts)."""
+    if shifts is None:
+        shifts = estimate_shifts(lasers, reduce="logsum", clamp=None, device=True)
+    return K.register_assemble(lasers, shifts, apply_mask=False)
+
+
+def segment_biofilm_2d(stack: torch.Tensor, keep: dict | None = None, epithelial: bool = True,
+                       disk_radius: int = 100, bkg_min_size: int = 10000):
+    """biofilm :347-418 (generate_2d_segmentation after the registration) on the registered
+    (H, W, C) stack.
+    -> (segmentation int32 relabelled 1..n, n, adjacency_seg int32 relabelled 1..n_adj, n_adj,
+        image_registered_sum f64, image_final_bkg_filtered f64, epithelial area u8 or None)
+
+    Cluster choices.  :367-377 (k = 2 on image_final) keeps the cluster whose positive values have
+    the larger mean, sklearn's cluster 0 on a NaN mean: kernels.kmeans_1d rule 1, as in
+    segment_multispecies.  :384-392 fits k = 2 on log10(nl) but compares i0, i1 = the means of the
+    raw registered sum over each cluster's positive pixels (kernels.cluster_positive_means; NaN for
+    a cluster without one) and keeps cluster 1 iff i0 < i1, else cluster 0.  The sums are
+    fixed-order tree sums, not numpy's pairwise sum over the boolean-compacted array: i0 and i1 can
+    differ from the reference's in the last bits, which matters only if they are equal to ~1e-15.
+    image_final_bkg_filtered is nl * mask (:393), not image_final * mask as in the multispecies
+    script.  The seeds of :399 / :400 are not multiplied by the flood mask (kernels.watershed floods
+    from markers outside it as skimage does).
+    An nl value <= 0 makes log10 -inf or NaN and the reference's KMeans raise: ValueError here.
+    epithelial: :404-418, the tissue side of the field -- the background of at least bkg_min_size
+    pixels, hole-filled, closed and then dilated by disk(disk_radius), the largest object of the
+    unmasked flood of -image_registered_sum from label(1 - dilated) taken as the biofilm and
+    everything else as epithelium.  Where the reference dies on argmax of an empty list (no
+    background component survives, or the dilated background covers the image) ValueError names
+    the stage.  False skips :404-418 and returns None.
+    keep: receives every intermediate by name, with the [contested, rounds, marker ties] lists of
+    the three floods (ties, ties_adjacency, ties_epithelial)."""
+    stack = K._dev(stack, torch.float32, "stack")
+    if stack.dim() != 3:
+        raise ValueError("segment_biofilm_2d: an (H, W, C) registered stack expected")
+    s = K.channel_sum(stack)                                                 # :347
+    norm = K.div_scalar(s, K.max_f64(s))                                     # :348
+    nl = K.nl_means_2d(norm, 7, 11, 0.02, 0.0)                               # :350 (:349 unused)
+    nonpos = K.count_nonzero(~(nl > 0))                                      # one count, before any fit
+    if nonpos:
+        raise ValueError("segment_biofilm_2d: %d pixels of the NL-means image are not positive, log10 is "
+                         "not finite there (:383-384)" % nonpos)
+    final = K.enhance_2d(K.pad_edge(nl, 5))                                  # :351-366
+    _, rough, cen_rough, _ = K.kmeans_1d(final, 2, want_labels=False, rule=1)    # :367-377
+    opened = K.binary_opening(rough)                                         # :378
+    small = K.remove_small_objects(opened, 10, conn=1)                       # :379
+    bfh = K.fill_holes(small)                                                # :380
+    rough_bfh = K.fill_holes(rough)                                          # :381
+    wmask_rough = K.and_mask(bfh, rough_bfh)                                 # :382
+    nl_log = K.log10(nl)                                                     # :383
+    blabels, _, cen_bkg, _ = K.kmeans_1d(nl_log, 2, want_labels=True)        # :384
+    sums, counts = K.cluster_positive_means(blabels, s, 2)                   # :385-388
+    i0, i1 = (sums / counts.double()).tolist()                               # 0 / 0 = NaN
+    bkg = (blabels == (1 if i0 < i1 else 0)).to(torch.uint8)                 # :389-392
+    final_bkg = K.mask_mul(nl, bkg)                                          # :393
+    sum_bkg = K.mask_mul(s, bkg)                                             # :394
+    wmask = K.remove_small_objects(K.and_mask(wmask_rough, bkg), 10, conn=1)     # :395-396
+    seeds, nseeds = K.label(wmask, conn=2)                                   # :397
+    flood_mask = K.and_mask(rough, bkg)                                      # :398
+    ties: list = []
+    ties_adj: list = []
+    ws = K.watershed(final_bkg, seeds, flood_mask, negate=True, ties=ties)   # :399
+    aws = K.watershed(sum_bkg, seeds, bkg, negate=True, ties=ties_adj)       # :400
+    seg, n = K.relabel_sequential(ws, nseeds)                                # :401
+    adj, n_adj = K.relabel_sequential(aws, nseeds)                           # :402
+    if keep is not None:
+        keep.update(image_sum=s, norm=norm, nl=nl, final=final, rough_mask=rough, opened=opened, small=small,
+                    bfh=bfh, rough_bfh=rough_bfh, nl_log=nl_log, bkg_labels=blabels, cluster_means=(i0, i1),
+                    bkg_mask=bkg, final_bkg=final_bkg, sum_bkg=sum_bkg, watershed_mask=wmask, seeds=seeds,
+                    nseeds=nseeds, flood_mask=flood_mask, watershed=ws, adjacency_watershed=aws, seg=seg,
+                    adjacency_seg=adj, centers_rough=cen_rough, centers_bkg=cen_bkg, ties=ties,
+                    ties_adjacency=ties_adj)
+    epi = None
+    if epithelial:
+        image_bkg = K.remove_small_objects(bkg == 0, bkg_min_size, conn=1)   # :404-405
+        image_bkg_bfh = K.fill_holes(image_bkg)                              # :406
+        closed = K.binary_closing_disk(image_bkg_bfh, disk_radius)           # :407-408
+        objects, nobj = K.label(closed, conn=2)                              # :409
+        big, _ = K.largest_label(objects, nobj)                              # :410-412
+        if big == 0:
+            raise ValueError("segment_biofilm_2d: no background component of %d pixels or more, the epithelial "
+                             "area's background is empty (:405-412)" % bkg_min_size)
+        bkg_final = (objects == big).to(torch.uint8)                         # :412
+        dilated = K.binary_dilation_disk(bkg_final, disk_radius)             # :413
+        overall, nover = K.label(1 - dilated, conn=2)                        # :414
+        if nover == 0:
+            raise ValueError("segment_biofilm_2d: the background dilated by disk(%d) covers the image, no object "
+                             "is left to flood from (:414-418)" % disk_radius)
+        ties_epi: list = []
+        overall_seg = K.watershed(s, overall, None, negate=True, ties=ties_epi)   # :415
+        biggest, _ = K.largest_label(overall_seg, nover)                     # :416-418
+        epi = (overall_seg != biggest).to(torch.uint8)                       # :418
+        if keep is not None:
+            keep.update(image_bkg=image_bkg, image_bkg_bfh=image_bkg_bfh, bkg_closed=closed, bkg_objects=objects,
+                        bkg_final=bkg_final, bkg_dilated=dilated, objects_overall=overall,
+                        objects_overall_seg=overall_seg, epithelial_area=epi, ties_epithelial=ties_epi)
+    return seg, n, adj, n_adj, s, final_bkg, epi
 
 
 # --------------------------------------------------------------------------------------------

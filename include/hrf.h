@@ -429,6 +429,40 @@ HRF_API hrf_status hrf_watershed3_heap(const double *image, int32_t negate, cons
                                        const uint8_t *mask, int64_t X, int64_t Y, int64_t Z, int32_t *out_labels,
                                        hrf_stream_t stream);
 
+/* ==== 2-D biofilm segmentation stages (biofilm2d.hip; biofilm_analysis.py:322-419) ========
+ * Binary dilation by skimage.morphology.disk(radius) = (X^2 + Y^2 <= radius^2) on [-radius, radius]^2
+ * (:407-413): out[p] = 1 iff a set pixel q inside the image has |p - q|^2 <= radius^2, which is
+ * scipy.ndimage.binary_dilation(mask, structure=disk(radius)); pixels outside the image read 0.
+ * Exact integer arithmetic in two passes -- the capped distance along each column to the nearest
+ * set pixel (u16), then per row the test g[y][x + d] <= floor(sqrt(radius^2 - d^2)) over |d| <=
+ * radius -- so the cost per pixel grows with radius, not with the disk's area.
+ * 1 <= radius <= 1023, H * W < 2^31 and H * ceil(W / 256) < 2^24.  work: hrf_disk_workspace_bytes
+ * device bytes (2 per pixel, rounded up); mask and out must not overlap.  Stream-ordered. */
+HRF_API int64_t hrf_disk_workspace_bytes(int64_t H, int64_t W, int32_t radius);
+HRF_API hrf_status hrf_binary_dilation_disk(const uint8_t *mask, int64_t H, int64_t W, int32_t radius, uint8_t *out,
+                                            void *work, int64_t work_bytes, hrf_stream_t stream);
+/* binary erosion by the same disk.  border_value 1 (skimage.morphology.binary_erosion): the
+ * complement, inside the image, of the dilation of the complement; border_value 0
+ * (scipy.ndimage's default): a pixel whose disk leaves the image is cleared as well. */
+HRF_API hrf_status hrf_binary_erosion_disk(const uint8_t *mask, int64_t H, int64_t W, int32_t radius,
+                                           int32_t border_value, uint8_t *out, void *work, int64_t work_bytes,
+                                           hrf_stream_t stream);
+/* out = log10(x) (:383) and out = log(x) (:327) on f64 with the correctly rounded hrf_cr_log10 /
+ * hrf_cr_log: -inf at 0, NaN below, +inf at +inf */
+HRF_API hrf_status hrf_log10_f64(const double *x, int64_t n, double *out, hrf_stream_t stream);
+HRF_API hrf_status hrf_log_f64(const double *x, int64_t n, double *out, hrf_stream_t stream);
+/* per cluster id c in 0..k-1 (k <= 64): sums[c], counts[c] = the sum and the number of values[i] with
+ * labels[i] == c and values[i] > 0 (:385-388; a NaN is not positive).  Fixed-order partial sums per
+ * workgroup and a fixed-order tree over them: the same (n, k) and data give the same bits on every
+ * run.  sums, counts: device, k entries. */
+HRF_API hrf_status hrf_cluster_positive_means(const int32_t *labels, const double *values, int64_t n, int32_t k,
+                                              double *sums, int64_t *counts, hrf_stream_t stream);
+/* out[0] = the label in 1..maxlab with the most pixels, the lowest among equals -- np.argmax over
+ * regionprops areas in label order (:411-412, :417-418) -- or 0 when none occurs; out[1] = its pixel
+ * count.  out: device, 2 int32; work: device, maxlab + 1 int32; n < 2^31. */
+HRF_API hrf_status hrf_largest_label(const int32_t *labels, int64_t n, int32_t maxlab, int32_t *out, int32_t *work,
+                                     hrf_stream_t stream);
+
 /* ==== native segmentation drivers (segment.hip) ==========================================
  * One call runs a whole segmentation chain -- the same library calls, in the same order, as
  * pipeline.segment_ecoli / segment_multispecies -- with device buffers owned by a context
