@@ -169,8 +169,10 @@ void oracle_svc_proba(const double *x, int64_t n, int64_t ldx, int f, const doub
     for (int a = 0; a < k; ++a)
       for (int b = a + 1; b < k; ++b, ++q) {
         double v = sigmoid_predict(dec[q], probA[q], probB[q]);
-        v = v < 1e-7 ? 1e-7 : v;
-        v = v > 1 - 1e-7 ? 1 - 1e-7 : v;
+        /* libsvm's min(max(v, 1e-7), 1 - 1e-7) with its own (x > y) ? x : y and (x < y) ? x : y:
+           a NaN fails the first comparison and becomes 1e-7 */
+        v = v > 1e-7 ? v : 1e-7;
+        v = v < 1 - 1e-7 ? v : 1 - 1e-7;
         r[a][b] = v;
         r[b][a] = 1 - v;
       }
