@@ -3,9 +3,9 @@
 //
 // Connected components (skimage.measure.label semantics: non-zero pixels connect when
 // EQUAL, 4- or 8-connectivity, raster-first numbering):
-//   1. cc_local   : 32x32 tile per workgroup, union-find in LDS with atomicMin linking
-//                   (larger root -> smaller root), so each local root is the tile-local
-//                   minimum index.
+//   1. cc_local   : 32x32 tile per workgroup, union-find in LDS (cc_core.hpp) with atomicMin
+//                   linking (larger root -> smaller root), so each local root is the
+//                   tile-local minimum index.
 //   2. cc_border  : the same union over tile-crossing neighbour pairs in global memory.
 //                   Reads may be stale; correctness comes from atomicMin's returned value
 //                   (retry on the true parent, indices strictly decrease).
@@ -15,73 +15,15 @@
 // Morphology kernels use the cross footprint of skimage's defaults.
 #include <algorithm>
 
+#include "cc_core.hpp"
 #include "common.hpp"
 #include "wave.hpp"
 
 namespace {
 
+using namespace hrf_cc;
+
 constexpr int CC_T = 32;  // tile edge
-
-struct MaskV {
-  const uint8_t *p;
-  int inv;
-  __device__ __forceinline__ int32_t operator()(int64_t i) const { return (int32_t)((p[i] != 0) ^ inv); }
-};
-struct LabelV {
-  const int32_t *p;
-  __device__ __forceinline__ int32_t operator()(int64_t i) const { return p[i]; }
-};
-
-__device__ __forceinline__ int find_lds(volatile int32_t *lp, int x) {
-  int y = lp[x];
-  while (y != x) {
-    x = y;
-    y = lp[x];
-  }
-  return x;
-}
-
-__device__ __forceinline__ void union_lds(int32_t *lp, int a, int b) {
-  volatile int32_t *v = lp;
-  for (;;) {
-    a = find_lds(v, a);
-    b = find_lds(v, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(&lp[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-__device__ __forceinline__ int32_t find_g(const int32_t *par, int32_t x) {
-  int32_t y = par[x];
-  while (y != x) {
-    x = y;
-    y = par[x];
-  }
-  return x;
-}
-
-__device__ __forceinline__ void union_g(int32_t *par, int32_t a, int32_t b) {
-  for (;;) {
-    a = find_g(par, a);
-    b = find_g(par, b);
-    if (a == b) return;
-    if (a < b) {
-      const int32_t t = a;
-      a = b;
-      b = t;
-    }
-    const int32_t old = atomicMin(&par[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 // zero != nullptr: also clears that per-pixel array (the component sizes the fused
 // compression pass counts into)

@@ -8,6 +8,7 @@
 // undirected edge (a, b), a, b >= 1 into +1 at adj[bc[a]][bc[b]] and adj[bc[b]][bc[a]]
 // (the reference visits each edge from both endpoints).
 #include "common.hpp"
+#include "rag_core.hpp"
 
 namespace {
 
@@ -33,38 +34,15 @@ __global__ void rag_mark_kernel(const int32_t *__restrict__ lab, int64_t H, int6
   }
 }
 
-__global__ void rag_count_kernel(const uint8_t *__restrict__ edge, int64_t L, const int32_t *__restrict__ bc,
-                                 int32_t R, unsigned long long *__restrict__ adj) {
-  const int64_t n = L * L;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    if (!edge[e]) continue;
-    const int64_t a = e / L, b = e - a * L;
-    if (a < 1 || b <= a) continue;
-    const int32_t ba = bc[a], bb = bc[b];
-    if (ba < 0 || ba >= R || bb < 0 || bb >= R) continue;
-    atomicAdd(&adj[(int64_t)ba * R + bb], 1ull);
-    atomicAdd(&adj[(int64_t)bb * R + ba], 1ull);
-  }
-}
-
-// raw and "cell"-filtered counts in one pass (biofilm :1290-1291: the filtered matrix counts an
-// edge only when both endpoint rows are typed 'cell')
+// every marked edge counted (rag_core.hpp): raw and, with keep and adjf, "cell"-filtered in one pass
 __global__ void rag_count2_kernel(const uint8_t *__restrict__ edge, int64_t L, const int32_t *__restrict__ bc,
                                   const uint8_t *__restrict__ keep, int32_t R, unsigned long long *__restrict__ adj,
                                   unsigned long long *__restrict__ adjf) {
   const int64_t n = L * L;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
     if (!edge[e]) continue;
-    const int64_t a = e / L, b = e - a * L;
-    if (a < 1 || b <= a) continue;
-    const int32_t ba = bc[a], bb = bc[b];
-    if (ba < 0 || ba >= R || bb < 0 || bb >= R) continue;
-    atomicAdd(&adj[(int64_t)ba * R + bb], 1ull);
-    atomicAdd(&adj[(int64_t)bb * R + ba], 1ull);
-    if (keep[a] && keep[b]) {
-      atomicAdd(&adjf[(int64_t)ba * R + bb], 1ull);
-      atomicAdd(&adjf[(int64_t)bb * R + ba], 1ull);
-    }
+    const int64_t a = e / L;
+    hrf::count_edge(a, e - a * L, bc, keep, R, adj, adjf);
   }
 }
 
@@ -114,7 +92,8 @@ hrf_status hrf_barcode_adjacency(const uint8_t *edge, int32_t maxlab, const int3
   HRF_REQUIRE(maxlab >= 0 && R >= 1 && edge && bc_of_label && adj, "barcode_adjacency: bad arguments");
   const int64_t L = (int64_t)maxlab + 1;
   HRF_HIP(hipMemsetAsync(adj, 0, sizeof(int64_t) * (size_t)R * R, s));
-  rag_count_kernel<<<hrf::stream_grid(L * L), 256, 0, s>>>(edge, L, bc_of_label, R, (unsigned long long *)adj);
+  rag_count2_kernel<<<hrf::stream_grid(L * L), 256, 0, s>>>(edge, L, bc_of_label, nullptr, R,
+                                                             (unsigned long long *)adj, nullptr);
   HRF_LAUNCHED();
   return HRF_OK;
 }

@@ -2,7 +2,7 @@
 // :280-289): per-label voxel moments and the regionprops fields the 3-D report reads, the label
 // adjacency of skimage.future.graph.rag_boundary as a sparse set of edges, the barcode x barcode
 // counts over that set, and the identification colour planes in Blender's voxel order.
-// Volumes are row-major with Z fastest (voxel p = (x * Y + y) * Z + z), n = X*Y*Z < 2^31 - 2.
+// Volumes are vol.hpp's: row-major with Z fastest, n = X*Y*Z < 2^31 - 2.
 //
 // Moments follow stats.hip's moments_kernel: a wave holds 64 consecutive voxels, usually of one
 // Z line; each distinct label of the wave leaves it as one set of four integer atomics, a run of
@@ -11,31 +11,23 @@
 // Edges: rag_boundary's edge set is, per voxel v, (min over the footprint, v) and (v, max over the
 // footprint) where they differ from v (scipy's grey erosion / dilation with
 // generate_binary_structure(3, conn); its reflect border repeats voxels of the in-volume window).
-// A 4 x 4 x 64 brick is staged in LDS with a one-voxel halo, as volume.hip's watershed pass stages
-// its state; an interior voxel (min == max == v) touches no global memory.  Keys (a << 32) | b,
-// a < b, go into an open-addressing table: a probe reads with plain loads and only an empty slot
-// is claimed by a 64-bit compare-and-swap, so the boundary voxels of one face, which mostly re-find
-// their key, cost a load each.  A lane whose key equals its Z predecessor's leaves it to that lane.
+// A 4 x 4 x 64 brick is staged in LDS with a one-voxel halo (vol.hpp's brick and halo walk, as in
+// volume.hip's watershed pass); an interior voxel (min == max == v) touches no global memory.  Keys
+// (a << 32) | b, a < b, go into an open-addressing table: a probe reads with plain loads and only
+// an empty slot is claimed by a 64-bit compare-and-swap, so the boundary voxels of one face, which
+// mostly re-find their key, cost a load each.  A lane whose key equals its Z predecessor's leaves it
+// to that lane.
 //
 // Planes: plane[ch][(z * Y + y) * X + x] = colour[label(x, y, z)][ch] is a transpose of every
 // (X, Z) slab; a 64 x 64 tile of labels goes through LDS so that the label reads run along Z and
 // the plane writes along X.
-#include "common.hpp"
+#include "rag_core.hpp"
+#include "vol.hpp"
 #include "wave.hpp"
 
 namespace {
 
-hrf_status check_vol3(int64_t X, int64_t Y, int64_t Z, const char *who) {
-  HRF_REQUIRE(X >= 0 && Y >= 0 && Z >= 0, "%s: negative extent", who);
-  bool ok = true;
-  if (X > 0 && Y > 0 && Z > 0) {  // the product is formed only below the limit
-    constexpr int64_t lim = ((int64_t)1 << 31) - 2;
-    ok = X < lim && Y < lim && X * Y < lim && Z < lim && (X * Y) <= (lim - 1) / Z;
-  }
-  HRF_REQUIRE(ok, "%s: volume too large (%lld x %lld x %lld, limit 2^31 - 2 voxels)", who, (long long)X, (long long)Y,
-              (long long)Z);
-  return HRF_OK;
-}
+using namespace hrf_vol;
 
 // ---- moments ------------------------------------------------------------------------------
 // mom[l * 4 ..] = {count, sum x, sum y, sum z}, exact
@@ -114,10 +106,6 @@ __global__ void props3_kernel(const unsigned long long *__restrict__ mom, int32_
 }
 
 // ---- edges --------------------------------------------------------------------------------
-constexpr int BX = 4, BY = 4, BZ = 64;                 // brick: 1024 voxels, 256 threads x 4
-constexpr int HX = BX + 2, HY = BY + 2, HZ = BZ + 2;  // with its halo
-constexpr int HV = HX * HY * HZ;
-constexpr int SZ = 1, SY = HZ, SX = HY * HZ;          // halo-index strides
 constexpr unsigned long long EMPTY = ~0ull;
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
@@ -156,20 +144,18 @@ __global__ __launch_bounds__(256) void rag_edges3_kernel(const int32_t *__restri
   const int64_t nbr = (int64_t)nbx * nby * nbz;
   int inserted = 0;
   for (int64_t br = blockIdx.x; br < nbr; br += gridDim.x) {
-    const int bz = (int)(br % nbz), by = (int)((br / nbz) % nby), bx = (int)(br / ((int64_t)nbz * nby));
-    const int64_t x0 = (int64_t)bx * BX - 1, y0 = (int64_t)by * BY - 1, z0 = (int64_t)bz * BZ - 1;
+    const Brick bk = brick_of(br, nby, nbz);
+    const int64_t x0 = bk.x0() - 1, y0 = bk.y0() - 1, z0 = bk.z0() - 1;
     __syncthreads();  // the previous brick's LDS is no longer read
     // a halo voxel outside the volume repeats the nearest voxel inside it: for a voxel v and an
     // offset d of its footprint, clamp(v + d) = v + d' with d' the offset d less its components
     // that leave the volume, which is again in the footprint (it has no more non-zero components)
-    for (int idx = tid; idx < HV; idx += 256) {
-      const int hx = idx / SX, hy = (idx - hx * SX) / SY, hz = idx - hx * SX - hy * SY;
-      int64_t gx = x0 + hx, gy = y0 + hy, gz = z0 + hz;
+    for_halo(tid, bk, Vol{X, Y, Z}, [&](int idx, int64_t gx, int64_t gy, int64_t gz, bool) {
       gx = gx < 0 ? 0 : (gx >= X ? X - 1 : gx);
       gy = gy < 0 ? 0 : (gy >= Y ? Y - 1 : gy);
       gz = gz < 0 ? 0 : (gz >= Z ? Z - 1 : gz);
       sv[idx] = lab[(gx * Y + gy) * Z + gz];
-    }
+    });
     __syncthreads();
     // thread tid owns the voxels (lx = k, ly = tid / 64, lz = tid % 64), k = 0..3
     const int ly = tid >> 6, lz = tid & 63;
@@ -210,22 +196,14 @@ __global__ __launch_bounds__(256) void rag_edges3_kernel(const int32_t *__restri
   if (lane == 0 && inserted) atomicAdd(info, inserted);
 }
 
-// rag_count2_kernel's rule over a list of keys
+// the edges' counts (rag_core.hpp) over a list of keys
 __global__ void adjacency_edges_kernel(const int64_t *__restrict__ keys, int64_t E, const int32_t *__restrict__ bc,
                                        const uint8_t *__restrict__ keep, int64_t maxlab, int32_t R,
                                        unsigned long long *__restrict__ adj, unsigned long long *__restrict__ adjf) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
     const unsigned long long key = (unsigned long long)keys[e];
     const int64_t a = (int64_t)(key >> 32), b = (int64_t)(key & 0xffffffffull);
-    if (a < 1 || b <= a || b > maxlab) continue;
-    const int32_t ba = bc[a], bb = bc[b];
-    if (ba < 0 || ba >= R || bb < 0 || bb >= R) continue;
-    atomicAdd(&adj[(int64_t)ba * R + bb], 1ull);
-    atomicAdd(&adj[(int64_t)bb * R + ba], 1ull);
-    if (adjf && keep && keep[a] && keep[b]) {
-      atomicAdd(&adjf[(int64_t)ba * R + bb], 1ull);
-      atomicAdd(&adjf[(int64_t)bb * R + ba], 1ull);
-    }
+    if (b <= maxlab) hrf::count_edge(a, b, bc, keep, R, adj, adjf);
   }
 }
 
@@ -271,7 +249,7 @@ hrf_status hrf_region_moments3(const int32_t *labels, int64_t X, int64_t Y, int6
                                hrf_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   HRF_REQUIRE(maxlab >= 0 && mom, "region_moments3: bad arguments");
-  HRF_TRY(check_vol3(X, Y, Z, "region_moments3"));
+  HRF_TRY(check_vol(X, Y, Z, "region_moments3"));
   HRF_HIP(hipMemsetAsync(mom, 0, sizeof(int64_t) * 4 * ((size_t)maxlab + 1), s));
   const int64_t n = X * Y * Z;
   if (n == 0) return HRF_OK;
@@ -298,7 +276,7 @@ hrf_status hrf_rag_edges3(const int32_t *labels, int64_t X, int64_t Y, int64_t Z
   HRF_REQUIRE(conn >= 1 && conn <= 3, "rag_edges3: conn must be 1, 2 or 3");
   HRF_REQUIRE(table && info_dev && cap >= 2 && cap <= ((int64_t)1 << 40) && (cap & (cap - 1)) == 0,
               "rag_edges3: the capacity must be a power of two >= 2");
-  HRF_TRY(check_vol3(X, Y, Z, "rag_edges3"));
+  HRF_TRY(check_vol(X, Y, Z, "rag_edges3"));
   HRF_HIP(hipMemsetAsync(table, 0xff, sizeof(uint64_t) * (size_t)cap, s));
   HRF_HIP(hipMemsetAsync(info_dev, 0, 2 * sizeof(int32_t), s));
   if (X * Y * Z == 0) return HRF_OK;
@@ -340,7 +318,7 @@ hrf_status hrf_barcode_adjacency_edges(const int64_t *keys, int64_t E, const int
 hrf_status hrf_paint_planes3(const int32_t *labels, int64_t X, int64_t Y, int64_t Z, const float *colour,
                              int32_t ncell, float *planes, hrf_stream_t stream) {
   HRF_REQUIRE(ncell >= 0 && colour, "paint_planes3: bad arguments");
-  HRF_TRY(check_vol3(X, Y, Z, "paint_planes3"));
+  HRF_TRY(check_vol(X, Y, Z, "paint_planes3"));
   if (X * Y * Z == 0) return HRF_OK;
   HRF_REQUIRE(labels && planes, "paint_planes3: null buffer");
   const int64_t ntx = hrf::cdiv(X, TP), ntz = hrf::cdiv(Z, TP);

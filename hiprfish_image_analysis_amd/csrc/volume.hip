@@ -1,114 +1,32 @@
 // volume.hip -- the 3-D segmentation stages (biofilm_analysis.py:818-859, :489-499): connected
 // components, cross-footprint morphology, fill-holes, small-object removal and the watershed on
-// (X, Y, Z) volumes, row-major with Z fastest (voxel p = (x * Y + y) * Z + z), n = X*Y*Z < 2^31 - 2.
+// (X, Y, Z) volumes.  The volume's layout and limit and the 4 x 4 x 64 brick are vol.hpp's.
 //
-// Components follow label.hip with a 4 x 4 x 64 brick (long in Z, the contiguous and short axis)
-// in place of the 32 x 32 tile: union-find in LDS per brick, the brick-crossing pairs merged in
-// global memory, then compression; parent[p] = the component's minimum raster index.  Numbering,
-// sizes and relabelling are label.hip's own entry points, which are flat in n.
+// Components: label.hip's three passes with the brick in place of the 32 x 32 tile and the same
+// union-find (cc_core.hpp): in LDS per brick, the brick-crossing pairs merged in global memory,
+// then compression; parent[p] = the component's minimum raster index.  Numbering, sizes and
+// relabelling are label.hip's own entry points, which are flat in n.
 //
-// The watershed follows watershed.hip on the 6-neighbour graph: the relaxation of (lambda, hop,
-// basin distance, label) in LDS bricks with ping-pong passes, then a count of the voxels whose
-// least-key labelled neighbours carry different labels.  None: the relaxation's labels are the
-// heap flood's (the order theorem of DESIGN.md "Watershed" is stated on the neighbour graph).
-// Any: the volume is flooded by the one-workgroup heap kernel (watershed.hip, six neighbours in
-// raster-offset order -X, -Y, -Z, +Z, +Y, +X) and its labels are returned; there is no 3-D
-// string-walk resolver.
+// The watershed is watershed.hip's on the 6-neighbour graph, by the same rule (ws_core.hpp: order,
+// initial state, transition): the relaxation of (lambda, hop, basin distance, label) in LDS bricks
+// with ping-pong passes, then a count of the voxels whose least-key labelled neighbours carry
+// different labels (ws3_contest_kernel).  None: the relaxation's labels are the heap flood's (the
+// order theorem of DESIGN.md "Watershed" is stated on the neighbour graph).  Any: the volume is
+// flooded by the one-workgroup heap kernel (watershed.hip, six neighbours in raster-offset order
+// -X, -Y, -Z, +Z, +Y, +X) and its labels are returned; there is no 3-D string-walk resolver.
 #include <algorithm>
 
-#include "common.hpp"
+#include "cc_core.hpp"
 #include "detmath.h"
+#include "vol.hpp"
 #include "wave.hpp"
+#include "ws_core.hpp"
 
 namespace {
 
-constexpr int BX = 4, BY = 4, BZ = 64;   // brick: 1024 voxels, 256 threads x 4
-constexpr int BV = BX * BY * BZ;
-constexpr int32_t HOP_INF = 0x7fffffff;
-
-struct Vol {
-  int64_t X, Y, Z;
-  __host__ __device__ int64_t n() const { return X * Y * Z; }
-  int64_t bx() const { return hrf::cdiv(X, BX); }
-  int64_t by() const { return hrf::cdiv(Y, BY); }
-  int64_t bz() const { return hrf::cdiv(Z, BZ); }
-  int64_t bricks() const { return bx() * by() * bz(); }
-};
-
-hrf_status check_vol(int64_t X, int64_t Y, int64_t Z, const char *who) {
-  HRF_REQUIRE(X >= 0 && Y >= 0 && Z >= 0, "%s: negative extent", who);
-  // the product is formed only below the limit
-  bool ok = true;
-  if (X > 0 && Y > 0 && Z > 0) {
-    constexpr int64_t lim = ((int64_t)1 << 31) - 2;
-    ok = X < lim && Y < lim && X * Y < lim && Z < lim && (X * Y) <= (lim - 1) / Z;
-  }
-  HRF_REQUIRE(ok, "%s: volume too large (%lld x %lld x %lld, limit 2^31 - 2 voxels)", who, (long long)X, (long long)Y,
-              (long long)Z);
-  return HRF_OK;
-}
-
-struct MaskV {
-  const uint8_t *p;
-  int inv;
-  __device__ __forceinline__ int32_t operator()(int64_t i) const { return (int32_t)((p[i] != 0) ^ inv); }
-};
-struct LabelV {
-  const int32_t *p;
-  __device__ __forceinline__ int32_t operator()(int64_t i) const { return p[i]; }
-};
-
-// ---- union-find (as label.hip: the larger root is linked under the smaller by atomicMin) ----
-__device__ __forceinline__ int find_lds(volatile int32_t *lp, int x) {
-  int y = lp[x];
-  while (y != x) {
-    x = y;
-    y = lp[x];
-  }
-  return x;
-}
-
-__device__ __forceinline__ void union_lds(int32_t *lp, int a, int b) {
-  volatile int32_t *v = lp;
-  for (;;) {
-    a = find_lds(v, a);
-    b = find_lds(v, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(&lp[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-__device__ __forceinline__ int32_t find_g(const int32_t *par, int32_t x) {
-  int32_t y = par[x];
-  while (y != x) {
-    x = y;
-    y = par[x];
-  }
-  return x;
-}
-
-__device__ __forceinline__ void union_g(int32_t *par, int32_t a, int32_t b) {
-  for (;;) {
-    a = find_g(par, a);
-    b = find_g(par, b);
-    if (a == b) return;
-    if (a < b) {
-      const int32_t t = a;
-      a = b;
-      b = t;
-    }
-    const int32_t old = atomicMin(&par[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
+using namespace hrf_cc;
+using namespace hrf_vol;
+using namespace hrf_ws;
 
 // the 13 neighbour offsets that precede a voxel in raster order, fewest non-zero components
 // first within each connectivity class: CONN 1 uses the first 3, CONN 2 the first 9, CONN 3 all
@@ -125,8 +43,8 @@ __global__ __launch_bounds__(256) void cc3_local_kernel(V val, Vol g, int nby, i
   __shared__ int32_t lp[BV];
   __shared__ int32_t lv[BV];
   const int tid = threadIdx.x;
-  const int64_t b = blockIdx.x;
-  const int64_t x0 = (b / ((int64_t)nby * nbz)) * BX, y0 = ((b / nbz) % nby) * BY, z0 = (b % nbz) * BZ;
+  const Brick bk = brick_of((int64_t)blockIdx.x, nby, nbz);
+  const int64_t x0 = bk.x0(), y0 = bk.y0(), z0 = bk.z0();
   const int ly = tid >> 6, lz = tid & 63;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -166,7 +84,7 @@ __global__ __launch_bounds__(256) void cc3_local_kernel(V val, Vol g, int nby, i
 }
 
 // The pairs (voxel, preceding neighbour) that cross a brick boundary, merged in global memory.
-// Reads may be stale; atomicMin's returned value makes the union exact (label.hip).
+// Reads may be stale; atomicMin's returned value makes the union exact (cc_core.hpp).
 template <class V, int CONN>
 __global__ void cc3_border_kernel(V val, Vol g, int32_t *__restrict__ parent) {
   const int64_t n = g.n();
@@ -270,10 +188,6 @@ __global__ void log10p1_kernel(const double *__restrict__ x, int64_t n, double *
 }
 
 // ---- watershed relaxation -------------------------------------------------------------------
-constexpr int HX = BX + 2, HY = BY + 2, HZ = BZ + 2;  // brick with its halo
-constexpr int HV = HX * HY * HZ;
-constexpr int SZ = 1, SY = HZ, SX = HY * HZ;          // halo-index strides
-
 struct WsState {
   double *lam;
   int32_t *hop;
@@ -293,7 +207,8 @@ __global__ __launch_bounds__(256) void ws3_init_kernel(const double *__restrict_
   const int tid = threadIdx.x;
   const int64_t nbr = gridDim.x, br = blockIdx.x;
   if (tid < 2) brick_flags[tid * nbr + br] = 0;  // change flags of generations 0 and 1
-  const int64_t x0 = (br / ((int64_t)nby * nbz)) * BX, y0 = ((br / nbz) % nby) * BY, z0 = (br % nbz) * BZ;
+  const Brick bk = brick_of(br, nby, nbz);
+  const int64_t x0 = bk.x0(), y0 = bk.y0(), z0 = bk.z0();
   const int ly = tid >> 6, lz = tid & 63;
   int work = 0, mark = 0;
 #pragma unroll
@@ -302,19 +217,17 @@ __global__ __launch_bounds__(256) void ws3_init_kernel(const double *__restrict_
     if (gx >= g.X || gy >= g.Y || gz >= g.Z) continue;
     const int64_t i = (gx * g.Y + gy) * g.Z + gz;
     const bool in = !mask || mask[i];
-    const int32_t m = in ? markers[i] : 0;
-    const double l = m ? (negate ? -f[i] : f[i]) : __builtin_inf();
-    const int32_t h = m ? 0 : HOP_INF;
-    a.lam[i] = l;
-    b.lam[i] = l;
-    a.hop[i] = h;
-    b.hop[i] = h;
-    a.dst[i] = h;
-    b.dst[i] = h;
-    a.lab[i] = m;
-    b.lab[i] = m;
-    work |= in && !m;
-    mark |= m != 0;
+    const WsCell c = ws_start(in, markers, f, negate, i);
+    a.lam[i] = c.lam;
+    b.lam[i] = c.lam;
+    a.hop[i] = c.hop;
+    b.hop[i] = c.hop;
+    a.dst[i] = c.dst;
+    b.dst[i] = c.dst;
+    a.lab[i] = c.lab;
+    b.lab[i] = c.lab;
+    work |= in && !c.lab;
+    mark |= c.lab != 0;
   }
   work = __syncthreads_or(work);
   mark = __syncthreads_or(mark);
@@ -325,20 +238,12 @@ __global__ __launch_bounds__(256) void ws3_init_kernel(const double *__restrict_
   }
 }
 
-__device__ __forceinline__ bool better(double l1, int32_t h1, int32_t d1, int32_t b1, double l2, int32_t h2,
-                                       int32_t d2, int32_t b2) {
-  if (l1 != l2) return l1 < l2;
-  if (h1 != h2) return h1 < h2;
-  if (d1 != d2) return d1 < d2;
-  return b1 < b2;
-}
-
-// One global pass: the relaxation of watershed.hip's ws_pass_kernel on a brick with a one-voxel
-// halo (20 B of state and a mask byte per voxel, 50 KB of LDS: three workgroups per CU).  A
-// resident grid walks the bricks; a brick with nothing relaxable, or whose own and six
-// face-adjacent bricks did not change in the previous pass, is skipped (a voxel reads only its
-// six neighbours, so no other brick's change can reach it in one pass).  Brick flags rotate
-// through three generations as the 2-D tile flags do.
+// One global pass: ws_core.hpp's relaxation, staged as in watershed.hip's ws_pass_kernel, on a
+// brick with a one-voxel halo (20 B of state and a mask byte per voxel, 50 KB of LDS: three
+// workgroups per CU).  A resident grid walks the bricks; a brick with nothing relaxable, or whose
+// own and six face-adjacent bricks did not change in the previous pass, is skipped (a voxel reads
+// only its six neighbours, so no other brick's change can reach it in one pass).  Brick flags
+// rotate through three generations as the 2-D tile flags do.
 __global__ __launch_bounds__(256) void ws3_pass_kernel(const double *__restrict__ f, int negate,
                                                        const int32_t *__restrict__ markers,
                                                        const uint8_t *__restrict__ mask, Vol g, WsState in,
@@ -356,7 +261,8 @@ __global__ __launch_bounds__(256) void ws3_pass_kernel(const double *__restrict_
   const int tid = threadIdx.x;
   const int nbr = nbx * nby * nbz;
   for (int br = blockIdx.x; br < nbr; br += gridDim.x) {
-    const int bz = br % nbz, by = (br / nbz) % nby, bx = br / (nbz * nby);
+    const Brick bk = brick_of(br, nby, nbz);
+    const int bx = bk.bx, by = bk.by, bz = bk.bz;
     if (tid == 0) next_brick[br] = 0;
     if (!brick_work[br]) continue;
     {
@@ -369,12 +275,10 @@ __global__ __launch_bounds__(256) void ws3_pass_kernel(const double *__restrict_
       if (bz + 1 < nbz) act |= prev_brick[br + 1];
       if (!act) continue;
     }
-    const int64_t x0 = (int64_t)bx * BX - 1, y0 = (int64_t)by * BY - 1, z0 = (int64_t)bz * BZ - 1;
+    const int64_t x0 = bk.x0() - 1, y0 = bk.y0() - 1, z0 = bk.z0() - 1;
     __syncthreads();  // the previous brick's LDS is no longer read
-    for (int idx = tid; idx < HV; idx += 256) {
-      const int hx = idx / SX, hy = (idx - hx * SX) / SY, hz = idx - hx * SX - hy * SY;
-      const int64_t gx = x0 + hx, gy = y0 + hy, gz = z0 + hz;
-      if (gx >= 0 && gx < g.X && gy >= 0 && gy < g.Y && gz >= 0 && gz < g.Z) {
+    for_halo(tid, bk, g, [&](int idx, int64_t gx, int64_t gy, int64_t gz, bool inside) {
+      if (inside) {
         const int64_t q = (gx * g.Y + gy) * g.Z + gz;
         const bool inm = !mask || mask[q];
         sl[idx] = in.lam[q];
@@ -389,7 +293,7 @@ __global__ __launch_bounds__(256) void ws3_pass_kernel(const double *__restrict_
         sb[idx] = 0;
         sm[idx] = 0;
       }
-    }
+    });
     __syncthreads();
     // thread tid owns the interior voxels (lx = k, ly = tid / 64, lz = tid % 64), k = 0..3; their
     // colour (lx + ly + lz) & 1 alternates with k
@@ -407,41 +311,22 @@ __global__ __launch_bounds__(256) void ws3_pass_kernel(const double *__restrict_
     auto relax = [&](int i, double fv) -> bool {
       if ((sm[i] & 3) != 1) return false;  // outside the mask (or the volume), or a marker
       const int nb[6] = {i - SX, i - SY, i - SZ, i + SZ, i + SY, i + SX};
-      double bl = __builtin_inf();
-      int32_t bh = HOP_INF, bd = HOP_INF, bb = 0;
+      WsCell best = ws_free();
 #pragma unroll
       for (int d = 0; d < 6; ++d) {
         const int j = nb[d];
         const int32_t bj = sb[j];
         if (!bj || !(sm[j] & 1)) continue;
-        if (better(sl[j], sh[j], sd[j], bj, bl, bh, bd, bb)) {
-          bl = sl[j];
-          bh = sh[j];
-          bd = sd[j];
-          bb = bj;
-        }
+        const WsCell c{sl[j], sh[j], sd[j], bj};
+        if (better(c, best)) best = c;
       }
-      if (!bb) return false;
-      double nl;
-      int32_t nh, nd;
-      if (bl < fv) {  // entry of level fv
-        nl = fv;
-        nh = 0;
-        nd = 0;
-      } else if (bl == fv) {  // plateau voxel: next FIFO layer
-        nl = bl;
-        nh = bh + 1;
-        nd = 0;
-      } else {  // basin voxel: filled in the slot that reached it
-        nl = bl;
-        nh = bh;
-        nd = bd + 1;
-      }
-      if (bb == sb[i] && nl == sl[i] && nh == sh[i] && nd == sd[i]) return false;
-      sl[i] = nl;
-      sh[i] = nh;
-      sd[i] = nd;
-      sb[i] = bb;
+      if (!best.lab) return false;
+      const WsCell c = ws_step(best, fv);
+      if (c.lab == sb[i] && c.lam == sl[i] && c.hop == sh[i] && c.dst == sd[i]) return false;
+      sl[i] = c.lam;
+      sh[i] = c.hop;
+      sd[i] = c.dst;
+      sb[i] = c.lab;
       return true;
     };
     bool any_change = false;

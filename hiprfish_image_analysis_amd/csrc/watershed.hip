@@ -17,7 +17,8 @@
 //    order of str(x) = key(x) . min_{c in C(x)} str(c) (a basin pixel: min_{c in C(x)} str(c);
 //    a marker: key . BOTTOM . raster index).  Candidates of different labels never share an
 //    ancestor, so the age a push receives inside one slot never decides a label.
-// Execution:
+// Execution (the rules themselves -- order, initial state, transition, contest, resolution -- are
+// ws_core.hpp's, shared with volume.hip and the CPU replay tools/ws_emul.cpp):
 //  1. relaxation of (lambda, h, label) -- ties to the smaller label -- in 32x32 LDS tiles,
 //     ping-pong global passes until no tile changes (ws_pass_kernel);
 //  2. ws_contest_kernel lists the pixels whose candidates carry different labels.  None (every
@@ -82,20 +83,18 @@ __global__ __launch_bounds__(256) void ws_init_kernel(const double *__restrict__
     if (gr >= H || gc >= W) continue;
     const int64_t i = gr * W + gc;
     const bool in = !mask || mask[i];
-    const int32_t m = in ? markers[i] : 0;
-    const double l = m ? (negate ? -f[i] : f[i]) : __builtin_inf();
-    const int32_t h = m ? 0 : HOP_INF;
-    a.lam[i] = l;
-    b.lam[i] = l;
-    a.hop[i] = h;
-    b.hop[i] = h;
-    a.dst[i] = h;
-    b.dst[i] = h;
-    a.lab[i] = m;
-    b.lab[i] = m;
+    const WsCell c = ws_start(in, markers, f, negate, i);
+    a.lam[i] = c.lam;
+    b.lam[i] = c.lam;
+    a.hop[i] = c.hop;
+    b.hop[i] = c.hop;
+    a.dst[i] = c.dst;
+    b.dst[i] = c.dst;
+    a.lab[i] = c.lab;
+    b.lab[i] = c.lab;
     ptr[i] = -1;
-    work |= in && !m;
-    mark |= m != 0;
+    work |= in && !c.lab;
+    mark |= c.lab != 0;
   }
   work = __syncthreads_or(work);
   mark = __syncthreads_or(mark);
@@ -103,14 +102,6 @@ __global__ __launch_bounds__(256) void ws_init_kernel(const double *__restrict__
     tile_work[blockIdx.y * gridDim.x + blockIdx.x] = work;
     tile_marker[blockIdx.y * gridDim.x + blockIdx.x] = mark;
   }
-}
-
-__device__ __forceinline__ bool better(double l1, int32_t h1, int32_t d1, int32_t b1, double l2, int32_t h2,
-                                       int32_t d2, int32_t b2) {
-  if (l1 != l2) return l1 < l2;
-  if (h1 != h2) return h1 < h2;
-  if (d1 != d2) return d1 < d2;
-  return b1 < b2;
 }
 
 // One global pass.  RELABEL = false: relax (lambda, h, d, label) from the least labelled
@@ -209,35 +200,21 @@ __global__ __launch_bounds__(256) void ws_pass_kernel(const double *__restrict__
     const int nbr[4] = {i - WL, i - 1, i + 1, i + WL};
     if (!RELABEL) {
       // first-popped neighbour = least (lambda, h) among labelled in-mask neighbours
-      double bl = __builtin_inf();
-      int32_t bh = HOP_INF, bd = HOP_INF, bb = 0;
+      WsCell best = ws_free();
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
         const int j = nbr[d];
         const int32_t bj = sb[j];
         if (!bj || !(sm[j] & 1)) continue;
-        if (better(sl[j], sh[j], sd[j], bj, bl, bh, bd, bb)) {
-          bl = sl[j];
-          bh = sh[j];
-          bd = sd[j];
-          bb = bj;
-        }
+        const WsCell c{sl[j], sh[j], sd[j], bj};
+        if (better(c, best)) best = c;
       }
-      if (bb) {
-        if (bl < fv) {  // entry of level fv
-          nl = fv;
-          nh = 0;
-          nd = 0;
-        } else if (bl == fv) {  // plateau pixel: next FIFO layer
-          nl = bl;
-          nh = bh + 1;
-          nd = 0;
-        } else {  // basin pixel: filled in the slot that reached it
-          nl = bl;
-          nh = bh;
-          nd = bd + 1;
-        }
-        nb = bb;
+      if (best.lab) {
+        const WsCell c = ws_step(best, fv);
+        nl = c.lam;
+        nh = c.hop;
+        nd = c.dst;
+        nb = c.lab;
       }
       return (nb != sb[i]) || (nl != sl[i]) || (nh != sh[i]) || (nd != sd[i]);
     }
@@ -329,11 +306,7 @@ __global__ void ws_contest_kernel(WsGeom g, const int32_t *__restrict__ lab, con
   const int64_t n = g.H * g.W;
   for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (int64_t)gridDim.x * blockDim.x) {
     if (!g_in(g, x) || g.mk[x] || g.lam[x] == __builtin_inf() || ptr[x] >= 0) continue;
-    int32_t cc[4];
-    const int m = g_cands(g, x, cc);
-    bool diff = false;
-    for (int j = 1; j < m; ++j) diff |= lab[cc[j]] != lab[cc[0]];
-    if (diff) list[atomicAdd(count, 1)] = (int32_t)x;
+    if (ws_contested(g, x, lab)) list[atomicAdd(count, 1)] = (int32_t)x;
   }
 }
 
@@ -734,43 +707,6 @@ __global__ __launch_bounds__(1024) void ws_heap_flood_kernel(const double *__res
 #endif
 }
 
-int64_t heap_flood_scratch_bytes(int64_t n) { return ((n + 2) * 16 + n * 4 + 255) & ~(int64_t)255; }
-
-hrf_status heap_flood(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask, int64_t H,
-                      int64_t W, int32_t *out, hipStream_t s) {
-  const int64_t n = H * W;
-  HRF_REQUIRE(n < ((int64_t)1 << 31) - 2, "watershed heap replay: image too large");
-  if (n == 0) return HRF_OK;
-  hrf::StreamBuf<char> scratch;
-  HRF_HIP(scratch.alloc((size_t)heap_flood_scratch_bytes(n), s));
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void *)ws_heap_flood_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)HEAP_LDS_BYTES) == hipSuccess &&
-           hipFuncSetAttribute((const void *)ws_heap_flood_kernel<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAP_LDS_BYTES) == hipSuccess;
-  }();
-  if (!attr) {
-    ::hrf::set_error("watershed heap replay: cannot reserve %d bytes of LDS", (int)HEAP_LDS_BYTES);
-    return HRF_EHIP;
-  }
-  char *base = scratch;
-  HeapItem *hp = (HeapItem *)base;
-  int32_t *lp = (int32_t *)(base + (n + 2) * 16);
-  if (mask)
-    ws_heap_flood_kernel<true><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H, (int32_t)W,
-                                                               out, hp, lp);
-  else
-    ws_heap_flood_kernel<false><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)H, (int32_t)W,
-                                                                out, hp, lp);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
-    return HRF_EHIP;
-  }
-  HRF_HIP(scratch.free());
-  return HRF_OK;
-}
-
 // ws_heap_flood_kernel on an (X, Y, Z) volume (volume.hip's tie path): the same heap and the same
 // two phases, six neighbours visited in raster-offset order -X, -Y, -Z, +Z, +Y, +X, which on a
 // volume with one axis of extent 1 is the 2-D kernel's up, left, right, down.  A kernel of its own,
@@ -862,6 +798,45 @@ __global__ __launch_bounds__(1024) void ws_heap_flood3_kernel(const double *__re
     }
     if ((fm >> lane) & 1ull) out[nbd] = lab;
   }
+}
+
+// The host side of both floods: the LDS attribute, the scratch (heap: (n + 2) items of 16 B;
+// list: n int32), the launch.  dims = the kernel's extents (H, W or X, Y, Z), n their product.
+template <auto K_MASK, auto K_NOMASK, class... Dims>
+hrf_status heap_flood_launch(const char *what, const double *image, int32_t negate, const int32_t *markers,
+                             const uint8_t *mask, int64_t n, int32_t *out, hipStream_t s, Dims... dims) {
+  HRF_REQUIRE(n < ((int64_t)1 << 31) - 2, "watershed heap replay: %s too large", what);
+  if (n == 0) return HRF_OK;
+  hrf::StreamBuf<char> scratch;
+  HRF_HIP(scratch.alloc((size_t)(((n + 2) * 16 + n * 4 + 255) & ~(int64_t)255), s));
+  static const bool attr = [] {
+    return hipFuncSetAttribute((const void *)K_MASK, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)HEAP_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute((const void *)K_NOMASK, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)HEAP_LDS_BYTES) == hipSuccess;
+  }();
+  if (!attr) {
+    ::hrf::set_error("watershed heap replay: cannot reserve %d bytes of LDS", (int)HEAP_LDS_BYTES);
+    return HRF_EHIP;
+  }
+  char *base = scratch;
+  HeapItem *hp = (HeapItem *)base;
+  int32_t *lp = (int32_t *)(base + (n + 2) * 16);
+  (mask ? K_MASK : K_NOMASK)<<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)dims..., out, hp,
+                                                             lp);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
+    return HRF_EHIP;
+  }
+  HRF_HIP(scratch.free());
+  return HRF_OK;
+}
+
+hrf_status heap_flood(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask, int64_t H,
+                      int64_t W, int32_t *out, hipStream_t s) {
+  return heap_flood_launch<ws_heap_flood_kernel<true>, ws_heap_flood_kernel<false>>("image", image, negate, markers,
+                                                                                    mask, H * W, out, s, H, W);
 }
 
 int64_t walker_bytes(int32_t cap, int32_t hcap, int32_t gcap) {
@@ -1073,37 +1048,8 @@ hrf_status hrf::watershed_ex_extra(const double *image, int32_t negate, const in
 // the heap flood of an (X, Y, Z) volume, X*Y*Z < 2^31 - 2 (checked by the caller, volume.hip)
 hrf_status hrf::heap_flood3(const double *image, int32_t negate, const int32_t *markers, const uint8_t *mask,
                             int64_t X, int64_t Y, int64_t Z, int32_t *out, hipStream_t s) {
-  const int64_t n = X * Y * Z;
-  HRF_REQUIRE(n < ((int64_t)1 << 31) - 2, "watershed heap replay: volume too large");
-  if (n == 0) return HRF_OK;
-  hrf::StreamBuf<char> scratch;
-  HRF_HIP(scratch.alloc((size_t)heap_flood_scratch_bytes(n), s));
-  static const bool attr = [] {
-    return hipFuncSetAttribute((const void *)ws_heap_flood3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)HEAP_LDS_BYTES) == hipSuccess &&
-           hipFuncSetAttribute((const void *)ws_heap_flood3_kernel<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAP_LDS_BYTES) == hipSuccess;
-  }();
-  if (!attr) {
-    ::hrf::set_error("watershed heap replay: cannot reserve %d bytes of LDS", (int)HEAP_LDS_BYTES);
-    return HRF_EHIP;
-  }
-  char *base = scratch;
-  HeapItem *hp = (HeapItem *)base;
-  int32_t *lp = (int32_t *)(base + (n + 2) * 16);
-  if (mask)
-    ws_heap_flood3_kernel<true><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)X, (int32_t)Y,
-                                                                (int32_t)Z, out, hp, lp);
-  else
-    ws_heap_flood3_kernel<false><<<1, 1024, HEAP_LDS_BYTES, s>>>(image, negate, markers, mask, (int32_t)X, (int32_t)Y,
-                                                                 (int32_t)Z, out, hp, lp);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ::hrf::set_error("watershed heap replay: launch failed: %s", hipGetErrorString(e));
-    return HRF_EHIP;
-  }
-  HRF_HIP(scratch.free());
-  return HRF_OK;
+  return heap_flood_launch<ws_heap_flood3_kernel<true>, ws_heap_flood3_kernel<false>>("volume", image, negate, markers,
+                                                                                      mask, X * Y * Z, out, s, X, Y, Z);
 }
 
 extern "C" {

@@ -1,5 +1,7 @@
-// ws_core.hpp -- the exact tie resolution of the watershed (watershed.hip), written once for
-// the device and for the host (tools/ws_emul.cpp replays the whole flow on the CPU to test it).
+// ws_core.hpp -- the watershed's rules, written once for the device and for the host: the
+// relaxation's order, initial state and transition (watershed.hip's 2-D tiles, volume.hip's 3-D
+// bricks), the contest decision and the exact tie resolution (watershed.hip).  tools/ws_emul.cpp
+// replays the whole 2-D flow on the CPU through this code to test it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,15 +31,52 @@ HRF_HD inline bool kless(double l1, int32_t h1, double l2, int32_t h2) {
   return l1 < l2 || (l1 == l2 && h1 < h2);
 }
 
-// candidates of x: in-mask reached neighbours with the least key
-HRF_HD inline int g_cands(const WsGeom &g, int64_t x, int32_t *out) {
+// ---- the relaxation's rule, for the 2-D tiles (watershed.hip), the 3-D bricks (volume.hip) and
+// the CPU replay (tools/ws_emul.cpp) ----
+struct WsCell {
+  double lam;
+  int32_t hop, dst, lab;  // dst: the distance into a basin from its slot (tie-break only)
+};
+
+// the order among labelled neighbours: the heap's key (lambda, hop), then dst, then the label
+HRF_HD __forceinline__ bool better(const WsCell &a, const WsCell &b) {
+  if (a.lam != b.lam) return a.lam < b.lam;
+  if (a.hop != b.hop) return a.hop < b.hop;
+  if (a.dst != b.dst) return a.dst < b.dst;
+  return a.lab < b.lab;
+}
+
+// not reached: a free pixel before the first pass, a cell off the image, "no neighbour yet"
+HRF_HD __forceinline__ WsCell ws_free() { return WsCell{__builtin_inf(), HOP_INF, HOP_INF, 0}; }
+
+// pixel i before the first pass: a marker inside the mask is reached at its own value
+HRF_HD __forceinline__ WsCell ws_start(bool in, const int32_t *mk, const double *f, int negate, int64_t i) {
+  const int32_t m = in ? mk[i] : 0;
+  return m ? WsCell{negate ? -f[i] : f[i], 0, 0, m} : ws_free();
+}
+
+// a pixel of value fv reached from its best labelled neighbour b
+HRF_HD __forceinline__ WsCell ws_step(const WsCell &b, double fv) {
+  if (b.lam < fv) return WsCell{fv, 0, 0, b.lab};              // entry of level fv
+  if (b.lam == fv) return WsCell{b.lam, b.hop + 1, 0, b.lab};  // plateau pixel: next FIFO layer
+  return WsCell{b.lam, b.hop, b.dst + 1, b.lab};               // basin pixel: filled in the slot that reached it
+}
+
+// the 4-neighbours of x inside the image, up, left, right, down
+HRF_HD inline int g_nbrs(const WsGeom &g, int64_t x, int64_t *nb) {
   const int64_t r = x / g.W, c = x - r * g.W;
-  int64_t nb[4];
   int k = 0;
   if (r > 0) nb[k++] = x - g.W;
   if (c > 0) nb[k++] = x - 1;
   if (c + 1 < g.W) nb[k++] = x + 1;
   if (r + 1 < g.H) nb[k++] = x + g.W;
+  return k;
+}
+
+// candidates of x: in-mask reached neighbours with the least key
+HRF_HD inline int g_cands(const WsGeom &g, int64_t x, int32_t *out) {
+  int64_t nb[4];
+  const int k = g_nbrs(g, x, nb);
   double bl = __builtin_inf();
   int32_t bh = HOP_INF;
   int m = 0;
@@ -55,6 +94,16 @@ HRF_HD inline int g_cands(const WsGeom &g, int64_t x, int32_t *out) {
     if (ly == bl && hy == bh) out[m++] = (int32_t)y;
   }
   return m;
+}
+
+// true when x's candidates carry different labels: only there can the heap's pop order decide a
+// label (volume.hip's ws3_contest_kernel decides the same over six neighbours, streaming)
+HRF_HD inline bool ws_contested(const WsGeom &g, int64_t x, const int32_t *lab) {
+  int32_t cc[4];
+  const int m = g_cands(g, x, cc);
+  bool diff = false;
+  for (int j = 1; j < m; ++j) diff |= lab[cc[j]] != lab[cc[0]];
+  return diff;
 }
 
 // Per-thread scratch: two member buffers (pixel, group), the basin slot list, a generation

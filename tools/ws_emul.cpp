@@ -1,6 +1,7 @@
-// ws_emul.cpp -- development tool: replays hrf_watershed_ex's flow on the CPU with the SAME
-// resolution code (csrc/ws_core.hpp), serially, so the tie logic can be checked against the
-// heap flood (oracle_watershed) without a GPU.  Not part of libhrf.so.
+// ws_emul.cpp -- development tool: replays hrf_watershed_ex's flow on the CPU, serially, with the
+// kernels' own rules (csrc/ws_core.hpp: the relaxation's order, initial state and transition, the
+// contest decision, the resolution), so they can be checked against the heap flood
+// (oracle_watershed) without a GPU.  Not part of libhrf.so.
 //   hipcc -O2 -fPIC -shared -o tools/libws_emul.so tools/ws_emul.cpp
 #include <cmath>
 #include <cstdlib>
@@ -13,13 +14,6 @@
 
 using namespace hrf_ws;
 
-static bool better(double l1, int32_t h1, int32_t d1, int32_t b1, double l2, int32_t h2, int32_t d2, int32_t b2) {
-  if (l1 != l2) return l1 < l2;
-  if (h1 != h2) return h1 < h2;
-  if (d1 != d2) return d1 < d2;
-  return b1 < b2;
-}
-
 extern "C" int ws_emul(const double *f, int negate, const int32_t *mk, const uint8_t *mask, int64_t H, int64_t W,
                        int32_t *out, int32_t *ties, int32_t *ptr_out = nullptr, double *lam_out = nullptr,
                        int32_t *hop_out = nullptr) {
@@ -27,52 +21,32 @@ extern "C" int ws_emul(const double *f, int negate, const int32_t *mk, const uin
   std::vector<double> lam(n);
   std::vector<int32_t> hop(n), lab(n), ptr(n, -1), dst(n);
   auto in = [&](int64_t i) { return !mask || mask[i]; };
+  WsGeom g{f, negate, mk, mask, H, W, lam.data(), hop.data()};
   for (int64_t i = 0; i < n; ++i) {
-    const int32_t m = in(i) ? mk[i] : 0;
-    lam[i] = m ? (negate ? -f[i] : f[i]) : INFINITY;
-    hop[i] = m ? 0 : HOP_INF;
-    dst[i] = m ? 0 : HOP_INF;
-    lab[i] = m;
+    const WsCell c = ws_start(in(i), mk, f, negate, i);
+    lam[i] = c.lam, hop[i] = c.hop, dst[i] = c.dst, lab[i] = c.lab;
   }
-  auto nbrs = [&](int64_t x, int64_t *nb) {
-    const int64_t r = x / W, c = x % W;
-    int k = 0;
-    if (r > 0) nb[k++] = x - W;
-    if (c > 0) nb[k++] = x - 1;
-    if (c + 1 < W) nb[k++] = x + 1;
-    if (r + 1 < H) nb[k++] = x + W;
-    return k;
-  };
-  for (bool ch = true; ch;) {  // relaxation, the pass kernel's rule
+  for (bool ch = true; ch;) {  // relaxation, the pass kernels' rule (ws_core.hpp)
     ch = false;
     for (int64_t x = 0; x < n; ++x) {
-      if (!in(x) || (in(x) && mk[x])) continue;
+      if (!in(x) || mk[x]) continue;
       int64_t nb[4];
-      const int k = nbrs(x, nb);
-      double bl = INFINITY;
-      int32_t bh = HOP_INF, bd = HOP_INF, bb = 0;
+      const int k = g_nbrs(g, x, nb);
+      WsCell best = ws_free();
       for (int j = 0; j < k; ++j) {
         const int64_t y = nb[j];
         if (!lab[y] || !in(y)) continue;
-        if (better(lam[y], hop[y], dst[y], lab[y], bl, bh, bd, bb)) bl = lam[y], bh = hop[y], bd = dst[y], bb = lab[y];
+        const WsCell c{lam[y], hop[y], dst[y], lab[y]};
+        if (better(c, best)) best = c;
       }
-      if (!bb) continue;
-      const double fv = negate ? -f[x] : f[x];
-      double nl;
-      int32_t nh, nd;
-      if (bl < fv) nl = fv, nh = 0, nd = 0;
-      else if (bl == fv) nl = bl, nh = bh + 1, nd = 0;
-      else nl = bl, nh = bh, nd = bd + 1;
-      if (nl != lam[x] || nh != hop[x] || nd != dst[x] || bb != lab[x]) {
-        lam[x] = nl;
-        hop[x] = nh;
-        dst[x] = nd;
-        lab[x] = bb;
+      if (!best.lab) continue;
+      const WsCell c = ws_step(best, g_f(g, x));
+      if (c.lam != lam[x] || c.hop != hop[x] || c.dst != dst[x] || c.lab != lab[x]) {
+        lam[x] = c.lam, hop[x] = c.hop, dst[x] = c.dst, lab[x] = c.lab;
         ch = true;
       }
     }
   }
-  WsGeom g{f, negate, mk, mask, H, W, lam.data(), hop.data()};
   const int32_t capx = getenv("WS_EMUL_CAPX") ? atoi(getenv("WS_EMUL_CAPX")) : 16;
   const int32_t cap = getenv("WS_EMUL_SMALL") ? 4096 : (int32_t)(capx * n + 64),
                 hcap = getenv("WS_EMUL_SMALL") ? 8192 : 1 << (int)std::ceil(std::log2(2.0 * (capx * n + 64))), gcap = cap;
@@ -88,11 +62,7 @@ extern "C" int ws_emul(const double *f, int negate, const int32_t *mk, const uin
     std::vector<int32_t> list;
     for (int64_t x = 0; x < n; ++x) {
       if (!in(x) || mk[x] || lam[x] == INFINITY || ptr[x] >= 0) continue;
-      int32_t cc[4];
-      const int m = g_cands(g, x, cc);
-      bool diff = false;
-      for (int j = 1; j < m; ++j) diff |= lab[cc[j]] != lab[cc[0]];
-      if (diff) list.push_back((int32_t)x);
+      if (ws_contested(g, x, lab.data())) list.push_back((int32_t)x);
     }
     if (list.empty()) break;
     total += (int32_t)list.size();
