@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void enhance2d_kernel(const double *__restrict
 // ------------------------------------------------------------------------------------
 // 3-D fused: patch 11, 72 directions.  Tile 4 x 4 x 32 outputs (z fastest), 2 voxels per
 // thread; 14 x 14 x 42 f64 LDS tile (65,856 B, 2 workgroups per CU).
-// MODE 0: final (X,Y,Z); MODE 1: per-direction normalised centre (X,Y,Z,72).
+// MODE 0: final (X,Y,Z); MODE 1: per-direction normalised centre (X,Y,Z,72); MODE 2: final in the
+// `+ 1e-8` form of the mosaic chain (biofilm :1114-1125).
 // ------------------------------------------------------------------------------------
 constexpr int E3_TX = 4, E3_TY = 4, E3_TZ = 32;
 constexpr int E3_LX = E3_TX + 10, E3_LY = E3_TY + 10, E3_LZ = E3_TZ + 10;
@@ -106,6 +107,10 @@ constexpr int E3_LX = E3_TX + 10, E3_LY = E3_TY + 10, E3_LZ = E3_TZ + 10;
 // tap is a number in [0, 1]), so every `a < b ? a : b` of the reference's min/max and of the
 // selection network picks the same value as v_min_f64 / v_max_f64 -- one instruction instead of a
 // compare, two 64-bit selects and their hazard nops (values equal => same bits, no signed zeros).
+// MODE 2 under the same condition: min and max are finite with |.| < 2^1023, so max - min is at most
+// 2^1024 - 2^971, the largest double, and r = (max - min) + 1e-8 is finite and >= 1e-8; c - min is
+// +0 or positive and finite (x - x is +0), so every v = (c - min) / r is a number >= +0, never NaN
+// and never -0, and the selection network again orders values whose equality means equal bits.
 #ifndef E3_GROUP_N
 #define E3_GROUP_N 4
 #endif
@@ -134,7 +139,8 @@ __device__ __forceinline__ void enhance3d_voxel(const double *__restrict__ b, in
       if (l == 5) c = q;
     }
     double r = mx - mn;
-    if (1e-8 > r) r = 1e-8;  // builtin max(range, 1e-8) (neighbor.pyx:259)
+    if (MODE == 2) r = r + 1e-8;  // :1116-1118, no clamp
+    else if (1e-8 > r) r = 1e-8;  // builtin max(range, 1e-8) (neighbor.pyx:259)
     v[t] = (c - mn) / r;
     // at most E3_GROUP directions' taps in flight: the 72 results stay within the register
     // budget of two waves per SIMD instead of the scheduler hoisting hundreds of LDS reads
@@ -168,7 +174,8 @@ __device__ __forceinline__ void enhance3d_voxel(const double *__restrict__ b, in
   // np.percentile(.., 25/75) over 72: positions 17.75 (t >= .5 form) and 53.25
   const double lq = v[18] - (v[18] - v[17]) * 0.25;
   const double uq = v[53] + (v[54] - v[53]) * 0.25;
-  const double qcv = nan_to_num((uq - lq) / (uq + lq));
+  const double qcv = MODE == 2 ? (uq - lq) / (uq + lq + 1e-8)  // :1123, no nan_to_num
+                               : nan_to_num((uq - lq) / (uq + lq));
   out[vox] = avg * (1.0 - qcv);
 }
 
@@ -204,6 +211,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const int64_t vox = (x * Y + y) * Z + z;
     if (fast) enhance3d_voxel<MODE, true>(b, vox, out);
     else enhance3d_voxel<MODE, false>(b, vox, out);
+  }
+}
+
+// hrf_enhance_3d_eps with a chunk: the voxels the reference's whole chunks do not reach stay 0
+__global__ __launch_bounds__(256) void zero_tail3_kernel(double *__restrict__ out, int64_t X, int64_t Y, int64_t Z,
+                                                         int64_t Xc, int64_t Yc) {
+  const int64_t n = X * Y * Z;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t xy = v / Z, y = xy % Y, x = xy / Y;
+    if (x >= Xc || y >= Yc) out[v] = 0.0;
   }
 }
 
@@ -416,6 +433,30 @@ hrf_status hrf_enhance_3d(const double *pad, int64_t xp, int64_t yp, int64_t zp,
   // 1024x1024x64 volume (round 4)
   enhance3d_kernel<0, 2><<<grid, 256, 0, (hipStream_t)stream>>>(pad, xp, yp, zp, final_, X, Y, Z);
   HRF_LAUNCHED();
+  return HRF_OK;
+}
+
+hrf_status hrf_enhance_3d_eps(const double *pad, int64_t xp, int64_t yp, int64_t zp, int32_t patch, int32_t ntheta,
+                              int32_t nphi, int64_t chunk, double *final_, hrf_stream_t stream) {
+  HRF_REQUIRE(patch == 11 && ntheta == 9 && nphi == 9,
+              "enhance_3d_eps: only the reference parameters (patch 11, theta 9, phi 9) are fused");
+  HRF_REQUIRE(xp >= 10 && yp >= 10 && zp >= 10, "enhance_3d_eps: padded volume smaller than patch");
+  HRF_REQUIRE(chunk >= 0, "enhance_3d_eps: chunk must be 0 (every voxel) or a positive size");
+  const int64_t X = xp - 10, Y = yp - 10, Z = zp - 10;
+  if (X == 0 || Y == 0 || Z == 0) return HRF_OK;
+  HRF_REQUIRE(pad && final_, "enhance_3d_eps: null buffer");
+  const int64_t Xc = chunk ? (X / chunk) * chunk : X, Yc = chunk ? (Y / chunk) * chunk : Y;
+  if (Xc > 0 && Yc > 0) {
+    // rows x >= Xc are not launched; a tile that straddles Yc is computed whole and cleared below
+    dim3 grid((unsigned)hrf::cdiv(Z, E3_TZ), (unsigned)hrf::cdiv(Yc, E3_TY), (unsigned)hrf::cdiv(Xc, E3_TX));
+    HRF_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "enhance_3d_eps: volume too large");
+    enhance3d_kernel<2, 2><<<grid, 256, 0, (hipStream_t)stream>>>(pad, xp, yp, zp, final_, Xc, Y, Z);
+    HRF_LAUNCHED();
+  }
+  if (Xc < X || Yc < Y) {
+    zero_tail3_kernel<<<hrf::stream_grid(X * Y * Z), 256, 0, (hipStream_t)stream>>>(final_, X, Y, Z, Xc, Yc);
+    HRF_LAUNCHED();
+  }
   return HRF_OK;
 }
 

@@ -381,6 +381,14 @@ def load_image_zstack_fixed_t_tile(path, t, tile, rescale=True):
     return load_image_zstack_fixed_t_memory_efficient(path, t, 0, get_z_range(path), tile, rescale)
 
 
+def load_mosaic_tstacks(path, rescale=True):
+    """every tile of a square mosaic (biofilm :1066-1072): a list over the get_tile_size(path)**2
+    tiles, in series order k = i * n + j, of lists over t of (H, W, Z, C) z-stacks, read one series
+    at a time (load_image_zstack_fixed_t_tile)"""
+    n, nt = get_tile_size(path), get_t_range(path)
+    return [[load_image_zstack_fixed_t_tile(path, t, k, rescale) for t in range(nt)] for k in range(n * n)]
+
+
 def load_ztslice(path, z_index, t_index, series=0, rescale=True, stitch=False):
     """bioformats.load_image(path, z=, t=) (biofilm :55-57): series 0 -- one tile, the size
     get_x_range / get_y_range report"""

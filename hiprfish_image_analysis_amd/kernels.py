@@ -98,6 +98,24 @@ def enhance_3d_v3(pad: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def enhance_3d_eps(pad: torch.Tensor, chunk: int | None = None) -> torch.Tensor:
+    """biofilm :1105-1126, the `+ 1e-8` form of the chain on a mosaic canvas -> final (X, Y, Z) f64:
+    per direction (c - mn) / ((mx - mn) + 1e-8), no nan_to_num and no clamp, the mean over the 72
+    directions, qcv = (uq - lq) / (uq + lq + 1e-8), final = mean * (1 - qcv).  chunk None: every
+    voxel; chunk c (the reference's 100): voxels with x >= (X // c) * c or y >= (Y // c) * c stay
+    0, as the reference's whole chunks leave them."""
+    pad = _dev(pad, torch.float64, "image_padded")
+    xp, yp, zp = pad.shape
+    if min(xp, yp, zp) < 10:
+        raise ValueError("negative dimensions are not allowed")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("enhance_3d_eps: chunk must be None or a positive size")
+    out = torch.empty((xp - 10, yp - 10, zp - 10), dtype=torch.float64, device=pad.device)
+    _lib.call("hrf_enhance_3d_eps", _ptr(pad), xp, yp, zp, 11, 9, 9, 0 if chunk is None else int(chunk), _ptr(out),
+              _stream())
+    return out
+
+
 # ---- helpers --------------------------------------------------------------------------------
 def _u8(t: torch.Tensor, name: str) -> torch.Tensor:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -455,6 +473,60 @@ def volume_channel_sum(vol, log=False, out=None):
     _lib.call("hrf_volume_assemble_dev", ctypes.cast(ptrs, ctypes.c_void_p), ch.ctypes.data, None, 1, X, Y, Z, 0,
               None, _ptr(out), int(bool(log)), _stream())
     return out
+
+
+def volume_tsum_masked(tstack, shifts):
+    """biofilm :203-236 and :1073-1076 with the shifts given: tstack a list of T (X, Y, Z, C) f32
+    time points of one mosaic tile, shifts (T, 3) int32 on the device (or host triples; row 0 is
+    not read).  Per channel tstack[0] + the zero-filled shifted later time points, added in f64 in
+    t order (no division by T, no rounding to f32), then np.sum(axis=3) in numpy's order; mask = the
+    AND over t >= 1 of each time point's coverage box (all ones for T = 1)
+    -> (sum * mask (X, Y, Z) f64, mask (X, Y, Z) u8) from one pass."""
+    import ctypes
+    tstack = _volumes(tstack, "volume_tsum_masked")
+    if any(v.shape != tstack[0].shape for v in tstack):
+        raise ValueError("volume_tsum_masked: the time points must share one shape")
+    X, Y, Z, C = tstack[0].shape
+    T = len(tstack)
+    sd = _shifts3(shifts, T, tstack[0].device, "volume_tsum_masked") if T > 1 else None
+    ptrs = (ctypes.c_void_p * T)(*[v.data_ptr() for v in tstack])
+    s = torch.empty((X, Y, Z), dtype=torch.float64, device=tstack[0].device)
+    m = torch.empty((X, Y, Z), dtype=torch.uint8, device=s.device)
+    _lib.call("hrf_volume_tsum_masked_dev", ctypes.cast(ptrs, ctypes.c_void_p), T, _ptr(sd), X, Y, Z, C, _ptr(s),
+              _ptr(m), _stream())
+    return s, m
+
+
+def mosaic_accumulate3(tile_sums, tile_masks, origins, canvas_shape, want_count=False):
+    """biofilm :1098-1101: the tiles' sum_filtered (X, Y, Z) f64 and coverage masks u8 placed on a
+    canvas of canvas_shape with tile k's first voxel at origins[k] (host triples).  Each canvas
+    voxel adds sum_filtered * mask of every tile whose box holds it in tile order, and is divided
+    by the number of those tiles whose mask is set there (0 -> 1) -> full f64 (with want_count also
+    that divisor, int32).  A box that leaves the canvas, or more than 64 tiles: HrfValueError with
+    nothing launched."""
+    import ctypes
+    sums = [_dev(s, torch.float64, "tile sum") for s in tile_sums]
+    masks = [_u8(m, "tile mask") for m in tile_masks]
+    nt = len(sums)
+    if nt < 1 or len(masks) != nt:
+        raise ValueError("mosaic_accumulate3: one mask per tile sum expected")
+    if sums[0].dim() != 3 or any(s.shape != sums[0].shape for s in sums) or any(m.shape != sums[0].shape for m in masks):
+        raise ValueError("mosaic_accumulate3: (X, Y, Z) tiles and masks of one shape expected")
+    org = _i32_host(origins).reshape(-1)
+    if org.size != 3 * nt:
+        raise ValueError("mosaic_accumulate3: one (x0, y0, z0) origin per tile expected")
+    TX, TY, TZ = sums[0].shape
+    CX, CY, CZ = (int(v) for v in canvas_shape)
+    dev = sums[0].device
+    sp = (ctypes.c_void_p * nt)(*[s.data_ptr() for s in sums])
+    mp = (ctypes.c_void_p * nt)(*[m.data_ptr() for m in masks])
+    if min(CX, CY, CZ) < 1:
+        raise _lib.HrfValueError("mosaic_accumulate3: empty canvas %s" % ((CX, CY, CZ),))
+    full = torch.empty((CX, CY, CZ), dtype=torch.float64, device=dev)
+    count = torch.empty((CX, CY, CZ), dtype=torch.int32, device=dev) if want_count else None
+    _lib.call("hrf_mosaic_accumulate3", ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(mp, ctypes.c_void_p),
+              org.ctypes.data, nt, TX, TY, TZ, CX, CY, CZ, _ptr(full), _ptr(count), _stream())
+    return (full, count) if want_count else full
 
 
 def pad_edge_3d(a, width=5):

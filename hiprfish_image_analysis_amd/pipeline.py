@@ -279,6 +279,133 @@ def register_volume_tstacks(tstacks, fill: str = "keep", want_sum: bool = False)
 
 
 # --------------------------------------------------------------------------------------------
+# Tiled 3-D mosaics (hiprfish_imaging_biofilm_analysis.py:1064-1172)
+# --------------------------------------------------------------------------------------------
+MOSAIC_MAX_TILES = 64
+
+
+def tile_tsum(tstack, want_shifts: bool = False):
+    """biofilm :203-236 and :1073-1076 on one mosaic tile: tstack a list of T (X, Y, Z, C) f32 time
+    points.  The shifts are estimated exactly as t_average_volume does (channel sums in numpy's
+    order, estimate_shifts3, no log, no clamp); the time points are shifted with zero fill, added
+    in f64 in t order and summed over C -> (sum_filtered (X, Y, Z) f64, mask u8[, shifts]): the
+    time sum times its coverage mask, and the mask (K.volume_tsum_masked).  One stream, nothing
+    synchronises."""
+    tstack = list(tstack)
+    T = len(tstack)
+    X, Y, Z, C = tstack[0].shape
+    sums = torch.empty((T, X, Y, Z), dtype=torch.float64, device=tstack[0].device)
+    if T > 1:
+        for i, a in enumerate(tstack):
+            K.channel_sum(a.reshape(X * Y, Z, C), out=sums[i].view(X * Y, Z))       # :206, :212
+    shifts = estimate_shifts3(sums)                                               # :213
+    s, m = K.volume_tsum_masked(tstack, shifts)                                   # :214-236, :1073-1076
+    return (s, m, shifts) if want_shifts else (s, m)
+
+
+def estimate_tile_shifts(sum_filtered_list, n: int, overlap: int = 50):
+    """biofilm :1077-1087: the shift of every tile of an n x n mosaic against its neighbour on the
+    `overlap`-voxel strips -> (n, n, 3) int32 device tensor.  Tile (0, 0): 0.  Column 0 of row
+    i > 0: [Tx-ov:Tx, :, :] of tile (i-1, 0) against [0:ov, :, :] of tile (i, 0).  Every other
+    tile: [:, Ty-ov:Ty, :] of its left neighbour against its own [:, 0:ov, :].  No clamp.  Strip
+    sizes are no powers of two, so every pair goes through K.register3_translations_dev (hipFFT).
+    Nothing synchronises."""
+    tiles = list(sum_filtered_list)
+    if n < 1 or len(tiles) != n * n:
+        raise ValueError("estimate_tile_shifts: n * n tiles expected")
+    Tx, Ty, Tz = tiles[0].shape
+    ov = int(overlap)
+    if not (1 <= ov <= min(Tx, Ty)):
+        raise ValueError("estimate_tile_shifts: overlap must lie in 1..min(Tx, Ty)")
+    out = torch.zeros((n, n, 3), dtype=torch.int32, device=tiles[0].device)         # :1077, :1081
+    for i in range(n):
+        for j in range(n):
+            if i == 0 and j == 0:
+                continue
+            if j == 0:
+                pair = (tiles[(i - 1) * n][Tx - ov:Tx], tiles[i * n][0:ov])         # :1083
+            else:
+                pair = (tiles[i * n + j - 1][:, Ty - ov:Ty], tiles[i * n + j][:, 0:ov])   # :1086
+            out[i, j] = K.register3_translations_dev(torch.stack(pair))[1]
+    return out
+
+
+def mosaic_origins(shifts, tile_shape, overlap: int = 50, margin: int = 10):
+    """biofilm :1092-1097 on the host: shifts an (n, n, 3) integer array -> (origins (n * n, 3)
+    int32 in tile order k = i * n + j, canvas shape (n Tx + 2 m, n Ty + 2 m, Tz + 2 m)).  The sums
+    are the reference's, with its asymmetry -- y and z do not accumulate column 0's shifts of
+    earlier rows:
+      x0 = i Tx - ov i + sum s[0:i+1, 0, 0] + sum s[i, 1:j+1, 0] + m
+      y0 = j Ty - ov j + sum s[i, 0:j+1, 1] + m
+      z0 = sum s[i, 0:j+1, 2] + m"""
+    import numpy as np
+    s = np.asarray(shifts, dtype=np.int64)
+    n = s.shape[0]
+    if s.shape != (n, n, 3):
+        raise ValueError("mosaic_origins: an (n, n, 3) array of shifts expected")
+    Tx, Ty, Tz = (int(v) for v in tile_shape)
+    ov, m = int(overlap), int(margin)
+    org = np.zeros((n * n, 3), dtype=np.int64)
+    for i in range(n):
+        for j in range(n):
+            org[i * n + j] = (i * Tx - ov * i + s[0:i + 1, 0, 0].sum() + s[i, 1:j + 1, 0].sum() + m,
+                              j * Ty - ov * j + s[i, 0:j + 1, 1].sum() + m,
+                              s[i, 0:j + 1, 2].sum() + m)
+    if np.abs(org).max() >= 2 ** 31:
+        raise K._lib.HrfValueError("mosaic_origins: origin outside int32")
+    return org.astype(np.int32), (n * Tx + 2 * m, n * Ty + 2 * m, Tz + 2 * m)
+
+
+def stitch_volume_tiles(tile_tstacks, n: int, overlap: int = 50, margin: int = 10):
+    """biofilm :1066-1102: tile_tstacks[k], k = i * n + j, the list of (X, Y, Z, C) f32 time
+    points of tile (i, j) of an n x n mosaic.  Each tile is summed over time with its coverage mask
+    (tile_tsum), registered to its neighbour on the overlap strips (estimate_tile_shifts), placed
+    on one canvas (mosaic_origins) and averaged over the overlaps (K.mosaic_accumulate3); the
+    canvas is divided by its maximum -> (norm (n Tx + 2 m, n Ty + 2 m, Tz + 2 m) f64, keep) with
+    keep a dict of the stages: sum_filtered, masks, t_shifts, shifts, origins, full, count.
+
+    Placement is decided on the host: the (n, n, 3) shifts are copied to the host once, which
+    synchronises the stream -- the only synchronisation here.  A tile box that leaves the canvas,
+    or more than 64 tiles, raises HrfValueError before the accumulation launches anything."""
+    tile_tstacks = list(tile_tstacks)
+    if n < 1 or len(tile_tstacks) != n * n:
+        raise ValueError("stitch_volume_tiles: n * n tiles expected")
+    if n * n > MOSAIC_MAX_TILES:
+        raise K._lib.HrfValueError("stitch_volume_tiles: at most %d tiles (got %d)" % (MOSAIC_MAX_TILES, n * n))
+    sums, masks, tsh = [], [], []
+    for ts in tile_tstacks:
+        s, m, sh = tile_tsum(ts, want_shifts=True)                                # :1069-1076
+        sums.append(s)
+        masks.append(m)
+        tsh.append(sh)
+    shifts = estimate_tile_shifts(sums, n, overlap)                               # :1077-1087
+    origins, canvas = mosaic_origins(shifts.cpu().numpy(), sums[0].shape, overlap, margin)   # the one D2H copy
+    full, count = K.mosaic_accumulate3(sums, masks, origins, canvas, want_count=True)        # :1088-1101
+    norm = K.div_scalar(full, K.max_f64(full))                                    # :1102
+    keep = dict(sum_filtered=sums, masks=masks, t_shifts=tsh, shifts=shifts, origins=origins, full=full, count=count)
+    return norm, keep
+
+
+def enhance_mosaic(norm: torch.Tensor, chunk: int | None = 100) -> torch.Tensor:
+    """biofilm :1103-1126: edge pad 5 and the `+ 1e-8` chain in the reference's chunks -> image_final"""
+    return K.enhance_3d_eps(K.pad_edge_3d(norm, 5), chunk)
+
+
+def segment_volume_mosaic(tile_tstacks, n: int, overlap: int = 50, margin: int = 10, chunk: int | None = 100,
+                          keep: dict | None = None):
+    """biofilm :1064-1172, generate_3d_segmentation_tile_memory_efficient: stitch_volume_tiles,
+    enhance_mosaic and segment_volume(background="log10eps_positive")
+    -> (segmentation int32 relabelled 1..n_cells, n_cells, final_bkg_filtered f64, norm f64).
+    keep: receives the stages of the stitch and of the segmentation, and final."""
+    norm, st = stitch_volume_tiles(tile_tstacks, n, overlap, margin)
+    final = enhance_mosaic(norm, chunk)
+    if keep is not None:
+        keep.update(st, norm=norm, final=final)
+    seg, ncell, final_bkg = segment_volume(final, norm, keep, background="log10eps_positive")
+    return seg, ncell, final_bkg, norm
+
+
+# --------------------------------------------------------------------------------------------
 # Biofilm 3-D enhancement input (hiprfish_imaging_biofilm_analysis.py:808-817)
 # --------------------------------------------------------------------------------------------
 def enhance_volume(stack: torch.Tensor, v3: bool = False) -> torch.Tensor:
@@ -310,9 +437,19 @@ def _enhance_norm(s: torch.Tensor, v3: bool = False) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 # Biofilm 3-D segmentation (hiprfish_imaging_biofilm_analysis.py:818-859, :489-499)
 # --------------------------------------------------------------------------------------------
-def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None = None, adjacency: bool = False):
+def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None = None, adjacency: bool = False,
+                   background: str = "log10p1"):
     """biofilm :818-859 on image_final and the normalised registered sum, both (X, Y, Z) f64.
     -> (segmentation int32 relabelled 1..n, n, final_bkg_filtered f64[, adjacency_seg, n_adj])
+
+    background "log10p1" (the default): the background filter of :845-854 as described below.
+    background "log10eps_positive": the mosaic's, :1154-1165 (:1127-1153 are :818-844 again) --
+    KMeans k = 2 on log10(reg_sum + 1e-8) (the correctly rounded log10), fitted only where
+    reg_sum > 0; the cluster means are taken on reg_sum itself, all of them positive, and 1-D
+    clusters are intervals, so the cluster with the larger mean of reg_sum is the one with the
+    larger centre in log10 and `i0 < i1` fails only when cluster 1 is empty (a NaN mean): the larger
+    cluster when both are non-empty, else cluster 0 -- rule 2.  Both branches of :1161-1165 leave
+    the mask false wherever reg_sum <= 0 (the margins and the voxels no tile covers).
 
     The KMeans cluster choices, read off the reference's comparisons of cluster means:
     :819-828 (k = 2 on final > 0) takes the cluster with the larger mean, sklearn's cluster 0 when
@@ -327,6 +464,8 @@ def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None
     reg_sum = K._dev(reg_sum, torch.float64, "reg_sum")
     if final.dim() != 3 or final.shape != reg_sum.shape:
         raise ValueError("segment_volume: final and reg_sum must be (X, Y, Z) volumes of one shape")
+    if background not in ("log10p1", "log10eps_positive"):
+        raise ValueError("segment_volume: background must be 'log10p1' or 'log10eps_positive'")
     pos = final > 0
     share: dict = {}
     _, rough, cen2, _ = K.kmeans_1d(final, 2, valid=pos, want_labels=False, share=share, rule=2)    # :818-828
@@ -337,8 +476,12 @@ def segment_volume(final: torch.Tensor, reg_sum: torch.Tensor, keep: dict | None
     rough_bfh = K.fill_holes3(rough)                                                # :842
     wmask = K.and_mask(bfh, rough_bfh)                                              # :843
     seeds, nseeds = K.label3(wmask, conn=3)                                         # :844
-    logsum = K.log10p1(reg_sum)              # :845, the correctly rounded log10 of channel_sum(mode=2)
-    _, bkg, cenb, _ = K.kmeans_1d(logsum, 2, want_labels=False, rule=1)             # :846-854
+    if background == "log10p1":
+        logsum = K.log10p1(reg_sum)          # :845, the correctly rounded log10 of channel_sum(mode=2)
+        _, bkg, cenb, _ = K.kmeans_1d(logsum, 2, want_labels=False, rule=1)         # :846-854
+    else:
+        logsum = K.log10(reg_sum + 1e-8)                                            # :1154
+        _, bkg, cenb, _ = K.kmeans_1d(logsum, 2, valid=reg_sum > 0, want_labels=False, rule=2)   # :1155-1165
     final_bkg = K.mask_mul(final, bkg)                                              # :855
     seeds_bkg = K.mask_labels(seeds, bkg)                                           # :856
     wmask_bkg = K.and_mask(wmask, bkg)                                              # :857

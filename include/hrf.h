@@ -87,6 +87,15 @@ HRF_API hrf_status hrf_enhance_3d(const double *pad, int64_t xp, int64_t yp, int
  * out (X,Y,Z) = mean * (p25 - p75) / (p25 + p75 + 1e-8). */
 HRF_API hrf_status hrf_enhance_3d_v3(const double *pad, int64_t xp, int64_t yp, int64_t zp, int32_t patch,
                                      int32_t ntheta, int32_t nphi, double *out, hrf_stream_t stream);
+/* the `+ 1e-8` form of the chain on a mosaic canvas (biofilm :1112-1125): per direction
+ * (centre - min) / ((max - min) + 1e-8) with no nan_to_num and no clamp, their mean in numpy's
+ * pairwise order, p25 / p75 by linear interpolation, final = mean * (1 - (p75 - p25) / (p75 + p25 +
+ * 1e-8)).  chunk 0: every voxel.  chunk c > 0 (:1105-1110, :1126 with c = 100): the reference walks
+ * (X / c) x (Y / c) whole chunks of c x c x Z -- the stencil is translation-invariant, so chunking
+ * changes no value -- and voxels with x >= (X / c) c or y >= (Y / c) c stay 0. */
+HRF_API hrf_status hrf_enhance_3d_eps(const double *pad, int64_t xp, int64_t yp, int64_t zp, int32_t patch,
+                                      int32_t ntheta, int32_t nphi, int64_t chunk, double *final_,
+                                      hrf_stream_t stream);
 
 
 /* ==== a1-a3: stack assembly and channel reductions (stack.hip) ======================== */
@@ -259,6 +268,34 @@ HRF_API hrf_status hrf_volume_assemble_dev(const float *const *src_host, const i
                                            const int32_t *shifts_dev, int32_t nlaser, int64_t X, int64_t Y, int64_t Z,
                                            int32_t fill, float *dst, double *sum_out, int32_t sum_mode,
                                            hrf_stream_t stream);
+
+/* ==== tiled 3-D mosaics (mosaic.hip) =======================================================
+ * biofilm :1064-1102 (generate_3d_segmentation_tile_memory_efficient).  Volumes are (X, Y, Z), Z
+ * fastest, X Y Z < 2^31 - 2 (HRF_EINVAL above).  Stream-ordered, no synchronisation.
+ *
+ * hrf_volume_tsum_masked_dev (:203-236, :1073-1076): src_host[t], t < T <= 16, the (X, Y, Z, C) f32
+ * time points of one tile, C <= 128; shifts and their convention as hrf_volume_taverage_dev (row 0
+ * is not read, T = 1: shifts_dev may be NULL; a shift of the extent or more leaves that time point
+ * no coverage).  Per channel src[0] + sum_{t >= 1} shift_zero(src[t]) added in f64 in t order -- not
+ * divided by T, not rounded to f32 -- then np.sum(axis=3) in numpy's pairwise order.  mask (X Y Z
+ * u8) = the AND over t >= 1 of each time point's coverage box, all ones for T = 1; sum_filtered
+ * (X Y Z f64) = sum * mask.  One pass: T C 4 bytes read and 9 written per voxel. */
+HRF_API hrf_status hrf_volume_tsum_masked_dev(const float *const *src_host, int32_t T, const int32_t *shifts_dev,
+                                              int64_t X, int64_t Y, int64_t Z, int32_t C, double *sum_filtered,
+                                              uint8_t *mask, hrf_stream_t stream);
+/* hrf_mosaic_accumulate3 (:1098-1101): ntiles <= 64 tiles of TX x TY x TZ placed on a CX x CY x CZ
+ * canvas with tile k's first voxel at origins_host[3k..3k+2] (host, int32; :1092-1097 decides
+ * them).  tile_sums_host / tile_masks_host: host arrays of the tiles' DEVICE sum_filtered / mask
+ * buffers.  Every canvas voxel adds sum_filtered * mask of each tile whose box holds it, in tile
+ * order k (the f64 order of the reference's `+=`; a gather, no atomics); its count is the number of
+ * those tiles whose mask is set there, 0 -> 1; full = sum / count, 0 under no tile.  count
+ * (nullable, int32) receives the divisor (>= 1).  A tile box that leaves the canvas on any side --
+ * the reference would wrap a negative index or fail to broadcast -- or more than 64 tiles:
+ * HRF_EINVAL before anything is launched. */
+HRF_API hrf_status hrf_mosaic_accumulate3(const double *const *tile_sums_host, const uint8_t *const *tile_masks_host,
+                                          const int32_t *origins_host, int32_t ntiles, int64_t TX, int64_t TY,
+                                          int64_t TZ, int64_t CX, int64_t CY, int64_t CZ, double *full,
+                                          int32_t *count, hrf_stream_t stream);
 
 /* ==== a4: non-local means (nlmeans.hip) ==================================================
  * skimage.restoration.denoise_nl_means(img, patch_size, patch_distance, h, fast_mode=True,
