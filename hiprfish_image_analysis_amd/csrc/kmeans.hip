@@ -21,6 +21,14 @@
 // rint(x * 2^s) in int64 (prefix sums over the value-sorted array, plus 128-bit prefix sums of
 // their squares), so every decision is independent of reduction order and equal to the CPU
 // restatement's bit for bit.
+// Value domain (km_scale; the same rule in kmeans_sk.c): the potential scale comes from frexp of
+// the range r = max - min, never of r * r.  Supported: 2^-481 <= r < 2^512 -- above, r * r
+// overflows; below, the scale 2^S that the potentials are multiplied by is no double (S > 1023;
+// r * r itself turns subnormal at 2^-511).  Outside it, r == 0 included, every squared distance
+// counts as zero (the factor g below), so every sample takes cluster 0 -- what sklearn's own
+// underflowed or overflowed squares give at magnitudes such as 1e-300 or 1e300.  A valid sample
+// that is NaN, infinite or above 2^1022 in magnitude sets error 1; 1 <= valid samples < k is
+// refused on the host before the fit is enqueued (sklearn raises ValueError for both).
 // Parity is pinned to sklearn 1.7.2 only.  The reference ran with the sklearn of its era
 // (0.20-0.22: first centre from randint, per-run int32 seeds, Elkan by default), whose random
 // streams differ; no fixture in the reference pins that, so parity with the reference-era
@@ -92,11 +100,6 @@ __host__ __device__ inline u128 thr_of(unsigned long long m, u128 T) {
   const u128 b = (u128)m * th;
   const u128 lo = a & ((((u128)1) << 53) - 1);
   return (a >> 53) + (b << 11) + (lo != 0 ? 1 : 0);
-}
-
-__host__ __device__ inline unsigned long long qd(double x, double c, double scaleS) {
-  const double d = x - c;
-  return (unsigned long long)(d * d * scaleS);
 }
 
 // ---- host: numpy RandomState replay --------------------------------------------------------
@@ -188,7 +191,8 @@ struct KmState {
   int s;          // value fixed point: q = rint(x * 2^s)
   int S;          // potential fixed point: floor(d^2 * 2^S)
   double tol;
-  int error;      // 1: NaN input (sklearn raises)
+  double g;       // 1, or 0 outside the value domain: (x - c) * g is squared
+  int error;      // 1: a NaN, infinite or > 2^1022 valid sample (sklearn raises)
   int best;       // winning run
   int top;        // sklearn id of the top cluster (by the rule)
   long long nle0; // samples <= 0 (rule 1)
@@ -225,7 +229,7 @@ __global__ void km_minmax_kernel(const double *__restrict__ x, const uint8_t *__
     for (int e = 0; e < 8; ++e) {
       if (!ok[e] || (valid && !valid[i + e * T])) continue;
       const double v = vv[e];
-      if (v != v) {
+      if (!(fabs(v) <= 0x1p1022)) {  // NaN, +-inf, or a magnitude whose range may overflow
         nn += 1;
         nv += 1;
         continue;
@@ -283,10 +287,14 @@ __device__ __forceinline__ void km_scale(KmState *st) {
   while ((1ull << ln) < (nv > 1 ? nv : 1ull)) ++ln;
   st->s = 61 - ln - e;
   const double mn = ord_dec(st->lo_bits), mx = ord_dec(st->hi_bits);
-  const double r = nv && !st->nnan ? mx - mn : 0.0, R2 = r * r;
-  int e2 = 0;
-  frexp(R2 > 0 ? R2 : 1.0, &e2);
-  st->S = 61 - e2;
+  // 2^(e2-1) <= fl(r * r) < 2^e2 from frexp(r) = (f, e): e2 = 2e - (f * f < 0.5); r * r itself
+  // is never formed (it overflows / underflows outside the domain, where g = 0 and S = 60)
+  const double r = nv && !st->nnan ? mx - mn : 0.0;
+  const bool normal = r >= 0x1p-481 && r < 0x1p512;  // 2^S a double (S <= 1023), r * r finite
+  int er = 0;
+  const double f = frexp(normal ? r : 1.0, &er);
+  st->S = normal ? 61 - (2 * er - (f * f < 0.5 ? 1 : 0)) : 60;
+  st->g = normal ? 1.0 : 0.0;
   st->error = st->nnan ? 1 : 0;
 }
 
@@ -750,23 +758,30 @@ __device__ __forceinline__ void km_tol(KmState *st) {
     st->tol = 0;
     return;
   }
-  const double m1 = (double)st->sumq / (double)nv, m2 = u128_to_double(U(st->sumq2)) / (double)nv;
-  st->tol = ldexp(m2 - m1 * m1, -2 * st->s) * 1e-4;
+  // n^2 var = n sum(q^2) - sum(q)^2, exact below 2^122 (|q| <= 2^(61 - ceil(log2 n))): the
+  // difference is taken in integers, so a mean far above the spread cancels nothing
+  const u128 nvar = (u128)(unsigned long long)nv * U(st->sumq2) - km_q2(st->sumq);
+  st->tol = ldexp(u128_to_double(nvar) / (double)nv / (double)nv, -2 * st->s) * 1e-4;
 }
 
 // ---- k-means++ -------------------------------------------------------------------------------
 // closest squared distance of v to the run's first c centres.  floor(. * 2^S) is monotone, so the
 // least fixed-point potential is the fixed point of the least square: one conversion per sample.
-__device__ __forceinline__ double closest_sq(double v, const double *cen, int c) {
-  double b = (v - cen[0]) * (v - cen[0]);
+__device__ __forceinline__ double sqd(double v, double c, double g) {
+  const double d = (v - c) * g;
+  return d * d;
+}
+__device__ __forceinline__ double closest_sq(double v, const double *cen, int c, double g) {
+  double b = sqd(v, cen[0], g);
   for (int j = 1; j < c; ++j) {
-    const double d = (v - cen[j]) * (v - cen[j]);
+    const double d = sqd(v, cen[j], g);
     b = d < b ? d : b;
   }
   return b;
 }
-__device__ __forceinline__ unsigned long long closest_q(double v, const double *cen, int c, double scaleS) {
-  return (unsigned long long)(closest_sq(v, cen, c) * scaleS);
+__device__ __forceinline__ unsigned long long closest_q(double v, const double *cen, int c, double scaleS,
+                                                        double g) {
+  return (unsigned long long)(closest_sq(v, cen, c, g) * scaleS);
 }
 
 // the first centre of every run: first[r]-th valid sample in raster order (xr compacted)
@@ -810,7 +825,7 @@ __global__ __launch_bounds__(PT) void km_pp_pass_kernel(const double *__restrict
       st->run[r].ncen = 1;
     }
   }
-  const double scaleS = ldexp(1.0, st->S);
+  const double scaleS = ldexp(1.0, st->S), g = st->g;
   const int64_t base = (int64_t)blockIdx.x * PB + threadIdx.x;
   double v[PB / PT];
   int cnt = 0;
@@ -824,7 +839,7 @@ __global__ __launch_bounds__(PT) void km_pp_pass_kernel(const double *__restrict
   for (int r = 0; r < d.nrun; ++r) {
     u128 s = 0;
 #pragma unroll
-    for (int e = 0; e < PB / PT; ++e) s += e < cnt ? closest_q(v[e], cen[r], c, scaleS) : 0ull;
+    for (int e = 0; e < PB / PT; ++e) s += e < cnt ? closest_q(v[e], cen[r], c, scaleS, g) : 0ull;
     const U128 tot = block_sum128(P(s), sh);
     if (threadIdx.x == 0) part[(int64_t)r * nblk + blockIdx.x] = tot;
   }
@@ -843,7 +858,7 @@ __global__ __launch_bounds__(PT) void km_pp_pick_kernel(const double *__restrict
   const int r = blockIdx.x / d.nt, t = blockIdx.x % d.nt;
   SkRun &R = st->run[r];
   const int64_t nv = (int64_t)st->nvalid;
-  const double scaleS = ldexp(1.0, st->S);
+  const double scaleS = ldexp(1.0, st->S), g = st->g;
   const int tid = threadIdx.x;
   const U128 *pr = part + (int64_t)r * nblk;
   const int per = (nblk + PT - 1) / PT;
@@ -884,7 +899,7 @@ __global__ __launch_bounds__(PT) void km_pp_pick_kernel(const double *__restrict
 #pragma unroll
     for (int e = 0; e < PB / PT; ++e) {
       const int64_t i = i0 + e;
-      cl[e] = i < nv ? closest_q(xr[i], R.cen, c, scaleS) : 0ull;
+      cl[e] = i < nv ? closest_q(xr[i], R.cen, c, scaleS, g) : 0ull;
       sthr += cl[e];
     }
     u128 tb;
@@ -969,7 +984,7 @@ __global__ __launch_bounds__(PT) void km_pp_corr_kernel(const double *__restrict
       if (p % NTMAX < d.nt) part2[(int64_t)p * nch + blockIdx.x] = U128{0ull, 0ull};
     return;
   }
-  const double scaleS = ldexp(1.0, st->S);
+  const double scaleS = ldexp(1.0, st->S), g = st->g;
   double v[PB / PT];
 #pragma unroll
   for (int e = 0; e < PB / PT; ++e) {
@@ -989,7 +1004,7 @@ __global__ __launch_bounds__(PT) void km_pp_corr_kernel(const double *__restrict
     unsigned long long dcq[PB / PT];
 #pragma unroll
     for (int e = 0; e < PB / PT; ++e) {
-      dc[e] = closest_sq(v[e], cen[r], c);
+      dc[e] = closest_sq(v[e], cen[r], c, g);
       dcq[e] = (unsigned long long)(dc[e] * scaleS);
     }
     for (int t = 0; t < d.nt; ++t) {
@@ -1001,7 +1016,7 @@ __global__ __launch_bounds__(PT) void km_pp_corr_kernel(const double *__restrict
 #pragma unroll
       for (int e = 0; e < PB / PT; ++e) {
         const long long i = c0 + (long long)e * PT + threadIdx.x;
-        const double dt = (v[e] - cv) * (v[e] - cv);
+        const double dt = sqd(v[e], cv, g);
         if (i >= a && i < b && i < c1 && dt < dc[e]) s += dcq[e] - (unsigned long long)(dt * scaleS);
       }
       const U128 w = wave_sum128(P(s));
@@ -1054,12 +1069,12 @@ static_assert(KS_T * KS_P == 4096, "index arithmetic below shifts by 12");
 
 // label of v: sklearn id of the first minimum of (v - c_j)^2 in sklearn order
 template <int K>
-__device__ __forceinline__ int sk_assign(double v, const double *c) {
+__device__ __forceinline__ int sk_assign(double v, const double *c, double g) {
   int bj = 0;
-  double bd = (v - c[0]) * (v - c[0]);
+  double bd = ((v - c[0]) * g) * ((v - c[0]) * g);
 #pragma unroll
   for (int j = 1; j < K; ++j) {
-    const double dd = (v - c[j]) * (v - c[j]);
+    const double dd = ((v - c[j]) * g) * ((v - c[j]) * g);
     if (dd < bd) {
       bd = dd;
       bj = j;
@@ -1082,6 +1097,7 @@ __device__ void km_bucket_step(const double *__restrict__ xs, const long long *_
                                const double *c, const int *pos, const double *cso, int j, int64_t *cnt_le,
                                long long *sum_le, U128 *sq_le) {
   const int t = threadIdx.x;
+  const double g = st->g;
   __shared__ int64_t lo_sh, hi_sh;
   __shared__ int bf_sh, bt_sh, exh_sh;
   __shared__ unsigned long long nf_sh;
@@ -1112,7 +1128,7 @@ __device__ void km_bucket_step(const double *__restrict__ xs, const long long *_
       u128 qf = 0;
       for (int64_t idx = lo + t; idx < hi; idx += KS_T) {
         const double v = xs[idx];
-        if (pos[sk_assign<K>(v, c)] <= j) {
+        if (pos[sk_assign<K>(v, c, g)] <= j) {
           const long long qi = km_q(v, s);
           nf += 1;
           sf += qi;
@@ -1158,7 +1174,7 @@ __device__ void km_bucket_step(const double *__restrict__ xs, const long long *_
       const int64_t idx = lo + ((len * (t * KS_P + p)) >> 12);  // KS_T * KS_P = 4096; len < 2^51
       const double v = xs[idx];
       const int b = km_bucket(v, mn, inv);
-      if (pos[sk_assign<K>(v, c)] <= j) bf = b > bf ? b : bf;
+      if (pos[sk_assign<K>(v, c, g)] <= j) bf = b > bf ? b : bf;
       else bt = b < bt ? b : bt;
     }
     if (bf >= 0) atomicMax(&bf_sh, bf);
@@ -1202,9 +1218,20 @@ __device__ void km_assign_all(const double *xs, const long long *bq, const U128 
     }
   }
   __syncthreads();
-  for (int j = 0; j + 1 < K; ++j)
-    if (cso[j] != cso[j + 1])
-      km_bucket_step<K>(xs, bq, bq2, off, st, nv, s, mn, inv, range, c, pos, cso, j, &cle[j], &sle[j], &qle[j]);
+  if (st->g == 0.0) {
+    // outside the value domain every squared distance is zero: all samples take sklearn's
+    // cluster 0 (the first minimum), whatever its sorted rank -- no step to search for
+    if (t < K - 1) {
+      const bool all = t >= pos[0];
+      cle[t] = all ? nv : 0;
+      sle[t] = all ? st->sumq : 0;
+      qle[t] = all ? st->sumq2 : U128{0ull, 0ull};
+    }
+  } else {
+    for (int j = 0; j + 1 < K; ++j)
+      if (cso[j] != cso[j + 1])
+        km_bucket_step<K>(xs, bq, bq2, off, st, nv, s, mn, inv, range, c, pos, cso, j, &cle[j], &sle[j], &qle[j]);
+  }
   __syncthreads();
   if (t == 0) {
     cle[K - 1] = nv;
@@ -1251,7 +1278,7 @@ __global__ __launch_bounds__(KS_T) void km_lloyd_kernel(const double *__restrict
   SkRun &R = st->run[r];
   const int64_t nv = (int64_t)st->nvalid;
   const int s = st->s;
-  const double mn = geo[0], inv = geo[1];
+  const double mn = geo[0], inv = geo[1], g = st->g;
   if (nv == 0 || st->error) {
     if (t == 0) {
       R.inertia = 0;
@@ -1288,8 +1315,7 @@ __global__ __launch_bounds__(KS_T) void km_lloyd_kernel(const double *__restrict
       }
       for (int64_t i = t; i < nv; i += KS_T) {
         const double v = xs[i];
-        const double cc = c[sk_assign<K>(v, c)];
-        const double dd = (v - cc) * (v - cc);
+        const double dd = sqd(v, c[sk_assign<K>(v, c, g)], g);
         for (int e = 0; e < m; ++e) {
           // later samples of this thread have larger positions: on equal (d, value) the
           // earlier one stays ahead
@@ -1352,7 +1378,7 @@ __global__ __launch_bounds__(KS_T) void km_lloyd_kernel(const double *__restrict
           if (cnt[j]) continue;
           const long long fi = far_sh[pk++];
           if (fi < 0) continue;
-          const int oj = sk_assign<K>(xs[fi], c);
+          const int oj = sk_assign<K>(xs[fi], c, g);
           const long long qf = km_q(xs[fi], s);
           sum[oj] -= qf;
           cnt[oj] -= 1;
@@ -1372,15 +1398,19 @@ __global__ __launch_bounds__(KS_T) void km_lloyd_kernel(const double *__restrict
         shift += dd * dd;
       }
       // labels equal to the previous iteration's: same cumulative counts and ids per
-      // non-empty sorted rank
+      // non-empty sorted rank, in order.  (Empty ranks are skipped on both sides: a relocated
+      // centre changes where the empty clusters sort without changing a label.)
       bool same = have_old;
-      if (same) {
-        for (int p = 0; p < K && same; ++p) {
-          const int64_t a0 = p ? cle[p - 1] : 0, b0 = p ? ocle[p - 1] : 0;
-          if (cle[p] != ocle[p]) same = false;
-          else if (cle[p] - a0 > 0 && ids[p] != oids[p]) same = false;
-          (void)b0;
+      for (int p = 0, q = 0; same;) {
+        while (p < K && cle[p] == (p ? cle[p - 1] : 0)) ++p;
+        while (q < K && ocle[q] == (q ? ocle[q - 1] : 0)) ++q;
+        if (p == K || q == K) {
+          same = p == K && q == K;
+          break;
         }
+        same = cle[p] == ocle[q] && ids[p] == oids[q];
+        ++p;
+        ++q;
       }
       for (int j = 0; j < K; ++j) {
         oldc[j] = c[j];
@@ -1424,8 +1454,11 @@ __global__ __launch_bounds__(KS_T) void km_lloyd_kernel(const double *__restrict
     double I = 0;
     for (int j = 0; j < K; ++j) {
       if (!n_of[j]) continue;
-      const double cs = ldexp(c[j], s);
-      I += (u128_to_double(q_of[j]) - 2.0 * cs * (double)s_of[j]) + (double)n_of[j] * cs * cs;
+      // sum (q - c)^2 = sum (q - mean)^2 + n (c - mean)^2; the first term as the exact integer
+      // n sum(q^2) - sum(q)^2 (below 2^122) over n: a mean far above the spread cancels nothing
+      const u128 nw = (u128)(unsigned long long)n_of[j] * q_of[j] - km_q2(s_of[j]);
+      const double dm = ldexp(c[j], s) - (double)s_of[j] / (double)n_of[j];
+      I += u128_to_double(nw) / (double)n_of[j] + (double)n_of[j] * dm * dm;
     }
     R.inertia = ldexp(I, -2 * s);
     for (int j = 0; j < K; ++j) {
@@ -1536,9 +1569,10 @@ __global__ void km_label_kernel(const double *__restrict__ x, const uint8_t *__r
   for (int j = 0; j < K; ++j) c[j] = B.lcen[j];
   const int jt = stop;
   const bool err = st->error != 0;
+  const double g = st->g;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const bool ok = (!valid || valid[i]) && !err;
-    const int bj = ok ? sk_assign<K>(x[i], c) : -1;
+    const int bj = ok ? sk_assign<K>(x[i], c, g) : -1;
     if (labels) labels[i] = bj;
     if (top) top[i] = (uint8_t)(bj == jt);
   }
@@ -1717,6 +1751,17 @@ hrf_status km_sk_launch(const double *x, const uint8_t *valid, int64_t n, int ma
     HRF_HIP(hipStreamSynchronize(s));
     nv = (int64_t)h;
   }
+  // sklearn raises for fewer samples than clusters; no valid sample at all stays what it was
+  // (labels -1, nothing fitted).  Every entry point comes through here (the single fit, the
+  // pair, the deferred pair of the native E. coli driver), so the message names none.  In a pair
+  // whose second k is the one refused, the first fit is already enqueued and this returns
+  // without a synchronisation: the stream orders that work before anything the caller enqueues
+  // next, and its outputs are the caller's buffers, so nothing is left to wait for.
+  if (nv >= 1 && nv < K) {
+    ::hrf::set_error("kmeans: n_samples=%lld should be >= n_clusters=%d (sklearn KMeans raises ValueError)",
+                     (long long)nv, K);
+    return HRF_EINVAL;
+  }
   const Draws d = make_draws(std::max<int64_t>(nv, 1), K, n_init, 0u);
   const double *xr = valid ? ws.xr : x;
   const int nblk = (int)nblocks(nv);
@@ -1762,6 +1807,14 @@ KmState *&last_single_state() {
   static thread_local KmState *fin = nullptr;
   return fin;
 }
+// whether that copy holds a completed fit: a refused or failed call leaves no records behind
+bool &last_single_valid() {
+  static thread_local bool ok = false;
+  return ok;
+}
+
+#define HRF_KM_BAD_VALUE "input contains NaN or infinity, or a finite magnitude above 2^1022 (sklearn KMeans raises " \
+                         "ValueError for NaN and infinity; two larger finite values can have an infinite range)"
 
 }  // namespace
 
@@ -1769,7 +1822,8 @@ extern "C" {
 
 hrf_status hrf_kmeans_last_runs(int32_t *iters, int32_t *relocations, int32_t *strict, int32_t n) {
   KmState *f = last_single_state();
-  HRF_REQUIRE(f && n >= 1 && n <= NRUN && iters, "kmeans_last_runs: no hrf_kmeans_1d_sorted call on this thread yet");
+  HRF_REQUIRE(f && last_single_valid(), "kmeans_last_runs: this thread's last hrf_kmeans_1d_sorted call did not complete a fit");
+  HRF_REQUIRE(n >= 1 && n <= NRUN && iters, "kmeans_last_runs: n must be 1..10");
   for (int r = 0; r < n; ++r) {
     iters[r] = f->run[r].iters;
     if (relocations) relocations[r] = f->run[r].reloc;
@@ -1812,12 +1866,14 @@ hrf_status hrf_kmeans_1d_sorted(const double *x, const uint8_t *valid, int64_t n
   const SortWs ws = carve(work, n, tb);
   hipStream_t s = (hipStream_t)stream;
   KmState *&fin = last_single_state();
+  last_single_valid() = false;
   // one pinned slot per host thread, process-lifetime by design
   if (!fin) HRF_HIP(hipHostMalloc((void **)&fin, sizeof(KmState), hipHostMallocDefault));
   if (hrf_status r = km_launch_k(k, x, valid, n, max_iter, n_init, top_rule, labels, top_mask, ws, reuse_sort, s, fin))
     return r;
   HRF_HIP(hipStreamSynchronize(s));
-  HRF_REQUIRE(!fin->error, "kmeans_1d: input contains NaN (sklearn KMeans raises ValueError)");
+  HRF_REQUIRE(!fin->error, "kmeans_1d: " HRF_KM_BAD_VALUE);
+  last_single_valid() = n > 0;
   if (centers_host)
     for (int j = 0; j < k; ++j) centers_host[j] = fin->center[j];
   if (iters_host) *iters_host = fin->iters;
@@ -1878,7 +1934,7 @@ hrf_status hrf_kmeans_1d_sorted_pair(const double *x, const uint8_t *valid, int6
   if (hrf_status r = km_launch_k(k1, x, valid, n, max_iter, n_init, rule1, nullptr, top1, ws, 0, s, nullptr)) return r;
   if (hrf_status r = km_launch_k(k2, x, valid, n, max_iter, n_init, rule2, nullptr, top2, ws, 1, s, fin)) return r;
   HRF_HIP(hipStreamSynchronize(s));
-  HRF_REQUIRE(!fin->error, "kmeans_1d_pair: input contains NaN (sklearn KMeans raises ValueError)");
+  HRF_REQUIRE(!fin->error, "kmeans_1d_pair: " HRF_KM_BAD_VALUE);
   return HRF_OK;
 }
 

@@ -175,7 +175,7 @@ static hrf_status segment_ecoli_from_cn(hrf_seg_ctx *c, const double *cn, int32_
     HRF_TRY(::hrf::zero_publish(zp, s));
   }
   HRF_HIP(hipStreamSynchronize(s));
-  HRF_REQUIRE(!c->hpin[3], "kmeans_1d_pair: input contains NaN (sklearn KMeans raises ValueError)");
+  HRF_REQUIRE(!c->hpin[3], "kmeans_1d_pair: input contains NaN or infinity, or a finite magnitude above 2^1022 (sklearn KMeans raises ValueError)");
   const int32_t ncomp = c->hpin[1];
   HRF_REQUIRE(ncomp >= 0, "segment_ecoli: component numbering failed");
   if (ncomp > guess) {

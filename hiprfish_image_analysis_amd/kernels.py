@@ -608,6 +608,8 @@ def kmeans_1d(x, k, valid=None, max_iter=300, want_labels=True, share=None, rule
     """sklearn KMeans(k, random_state=0, n_init=10).fit_predict on the values of x (kmeans.hip)
     -> labels int32 (sklearn's cluster ids, or None), top-cluster mask u8 (by `rule`, see
     include/hrf.h), centres (list, sklearn order), iterations.
+    ValueError (HrfValueError) where sklearn raises one: a valid sample that is NaN or infinity,
+    or 1 <= valid samples < k (the message names both numbers).
     share: a dict passed to successive calls on the SAME x / valid so the sort is done once."""
     import ctypes
     import numpy as np
@@ -650,6 +652,18 @@ def kmeans_1d_pair(x, k1, k2, valid=None, max_iter=300, rules=(2, 0), n_init=10)
     _lib.call("hrf_kmeans_1d_sorted_pair", _ptr(x), _ptr(v), n, k1, k2, max_iter, n_init, rules[0], rules[1],
               _ptr(top1), _ptr(top2), _ptr(ws), ws.numel(), _stream())
     return top1, top2
+
+
+def kmeans_last_runs(n_init=10):
+    """per-run records of this thread's last kmeans_1d call (every run, not only the winner):
+    int32 arrays of Lloyd iterations, empty-cluster relocations and strict-convergence flags.
+    ValueError when that call was refused or failed: an earlier fit's records are not handed out"""
+    import numpy as np
+    it = np.zeros(n_init, np.int32)
+    rel = np.zeros(n_init, np.int32)
+    strict = np.zeros(n_init, np.int32)
+    _lib.call("hrf_kmeans_last_runs", it.ctypes.data, rel.ctypes.data, strict.ctypes.data, n_init)
+    return it, rel, strict
 
 
 def kmeans_draws(nv, k, n_init=10):

@@ -315,13 +315,26 @@ HRF_API hrf_status hrf_nl_means_2d(const double *img, int64_t H, int64_t W, int3
  * (nullable) u8 = the cluster chosen by top_rule: 0 the largest centre; 1 (k = 2, multispecies
  * :126-135/:142-149) the larger cluster when both hold a positive value, else cluster 0; 2
  * (k = 2, ecoli :75-84) the larger cluster when both are non-empty, else cluster 0.
- * centers_host[k] / iters_host (nullable) receive sklearn's cluster_centers_ / n_iter_.  NaN
- * input -> HRF_EINVAL (sklearn raises).  work: hrf_kmeans_sorted_workspace_bytes(n) device
+ * centers_host[k] / iters_host (nullable) receive sklearn's cluster_centers_ / n_iter_.
+ * Refused with HRF_EINVAL, as sklearn raises ValueError: a valid sample that is NaN or infinite
+ * (or above 2^1022 in magnitude, whose range need not be finite), and 1 <= valid samples < k
+ * (the message names both numbers; in the pair, a refused second k leaves the first fit
+ * enqueued).  The first message names the 2^1022 bound, which sklearn does not have.  No valid sample at all, n == 0 included, is no error: labels
+ * -1, mask 0, centres 0.  Entries outside `valid` may hold anything, NaN and infinity included.
+ * Magnitude domain: squared distances order the samples where the range r = max - min of the
+ * valid samples satisfies 2^-481 <= r < 2^512 (about 1.6e-145 .. 1.3e154; the values themselves
+ * may be anything up to 2^1022).  Outside it (and for r == 0) every squared distance counts as
+ * zero: all valid samples take cluster 0 and empty clusters take the lowest values -- what
+ * sklearn's underflowed / overflowed squares give.  The variance behind the tolerance and
+ * the inertia that picks the winning run are differences of exact integer sums, so a mean far
+ * above the spread costs them no precision.
+ * work: hrf_kmeans_sorted_workspace_bytes(n) device
  * bytes; reuse_sort != 0: `work` already holds the sort of this very x / valid from a
  * previous call (e.g. k = 2 then k = 3 on ecoli image_cn).  Synchronises the stream once. */
 HRF_API int64_t hrf_kmeans_sorted_workspace_bytes(int64_t n);
 /* diagnostics: per-run Lloyd iterations, empty-cluster relocations and strict convergence of
- * this thread's last hrf_kmeans_1d_sorted call (n = its n_init) */
+ * this thread's last hrf_kmeans_1d_sorted call (n = its n_init); HRF_EINVAL when that call was
+ * refused or failed (no records of an earlier fit are handed out) */
 HRF_API hrf_status hrf_kmeans_last_runs(int32_t *iters, int32_t *relocations, int32_t *strict, int32_t n);
 HRF_API hrf_status hrf_kmeans_1d_sorted(const double *x, const uint8_t *valid, int64_t n, int32_t k, int32_t max_iter,
                                         int32_t n_init, int32_t top_rule, int32_t *labels, uint8_t *top_mask,

@@ -32,8 +32,27 @@
  * to sklearn 1.7.2 itself (tests/golden/kmeans_images.npz and random draws in
  * tests/test_oracle_golden.py).
  *
+ * Value domain (the same rule in kmeans.hip, km_scale): with r = max - min over the valid samples
+ * and frexp(r) = (f, e), the squared range lies in [2^(e2-1), 2^e2) for e2 = 2e - (f*f < 0.5),
+ * and S = 61 - e2.  The exponent is never read off r*r itself, which overflows above
+ * r ~ 1.3e154 and underflows below r ~ 1.5e-154.  Supported: 2^-481 <= r < 2^512.  Above it r*r
+ * overflows; below it 2^S, which the device multiplies the squares by, is no double (S > 1023;
+ * r*r itself turns subnormal at r = 2^-511, so between 2^-511 and 2^-481 sklearn still clusters
+ * and this definition does not).  Outside the domain, r == 0 included, every squared distance
+ * counts as zero (g = 0 below; S = 60 as for a constant input), so every potential is zero,
+ * every sample takes sklearn's cluster 0 and empty clusters take the lowest values -- what
+ * sklearn's own overflowed or underflowed squares give at magnitudes such as 1e-300, 1e-170,
+ * 1e160 and 1e300.
+ *
+ * Refused (sklearn raises ValueError; return value 1 / 2, nothing written but info[0:4] = 0):
+ *  1: a valid sample is NaN, infinite or above 2^1022 in magnitude (the range of two such
+ *     values need not be finite);
+ *  2: 1 <= valid samples < k.  No valid sample at all is not an error (labels -1, centres 0).
+ *
  * info: [0] winning run, [1] its Lloyd iterations, [2] strict convergence of the winner,
  *       [3] empty-cluster relocations over all runs
+ * runs (oracle_kmeans_sk_runs, nullable): per run r, runs[3r] Lloyd iterations, runs[3r+1]
+ *       strict convergence, runs[3r+2] its empty-cluster relocations
  */
 #include <math.h>
 #include <stdint.h>
@@ -47,8 +66,8 @@ typedef unsigned __int128 u128;
 int oracle_kmeans_scale(double amax, int64_t n);
 
 /* squared distance in fixed point: floor(fl((x - c)^2) * 2^S) */
-static uint64_t qd(double x, double c, int S) {
-    const double d = x - c;
+static uint64_t qd(double x, double c, int S, double g) {
+    const double d = (x - c) * g;
     return (uint64_t)ldexp(d * d, S);
 }
 
@@ -67,14 +86,15 @@ typedef struct {
     int64_t n;           /* valid samples */
     const double *v;     /* valid values, raster order */
     int S, s;            /* potential / value fixed-point scales */
+    double g;            /* 1, or 0 outside the value domain */
 } kdata;
 
 /* assignment with centres in sklearn order: first minimum */
-static int assign(double x, const double *c, int k) {
+static int assign(double x, const double *c, int k, double g) {
     int bj = 0;
-    double bd = (x - c[0]) * (x - c[0]);
+    double bd = ((x - c[0]) * g) * ((x - c[0]) * g);
     for (int j = 1; j < k; ++j) {
-        const double d = (x - c[j]) * (x - c[j]);
+        const double d = ((x - c[j]) * g) * ((x - c[j]) * g);
         if (d < bd) {
             bd = d;
             bj = j;
@@ -93,7 +113,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
     cen[0] = v[first];
     u128 T = 0;
     for (int64_t i = 0; i < n; ++i) {
-        cl[i] = qd(v[i], cen[0], D->S);
+        cl[i] = qd(v[i], cen[0], D->S, D->g);
         T += cl[i];
     }
     for (int c = 1; c < k; ++c) {
@@ -115,7 +135,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
             const double cv = v[ci];
             u128 P = 0;
             for (int64_t i = 0; i < n; ++i) {
-                const uint64_t d = qd(v[i], cv, D->S);
+                const uint64_t d = qd(v[i], cv, D->S, D->g);
                 P += d < cl[i] ? d : cl[i];
             }
             if (!have || P < best_P) {
@@ -126,7 +146,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
         }
         cen[c] = best_v;
         for (int64_t i = 0; i < n; ++i) {
-            const uint64_t d = qd(v[i], best_v, D->S);
+            const uint64_t d = qd(v[i], best_v, D->S, D->g);
             if (d < cl[i]) cl[i] = d;
         }
         T = best_P;
@@ -143,7 +163,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
         memset(sum, 0, sizeof sum);
         memset(cnt, 0, sizeof cnt);
         for (int64_t i = 0; i < n; ++i) {
-            const int j = assign(v[i], cen, k);
+            const int j = assign(v[i], cen, k, D->g);
             lab[i] = j;
             sum[j] += llrint(ldexp(v[i], D->s));
             cnt[j] += 1;
@@ -164,7 +184,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
                     int taken = 0;
                     for (int q = 0; q < np; ++q) taken |= pick[q] == i;
                     if (taken) continue;
-                    const double d = (v[i] - cen[lab[i]]) * (v[i] - cen[lab[i]]);
+                    const double d0 = (v[i] - cen[lab[i]]) * D->g, d = d0 * d0;
                     if (d > bd || (d == bd && (v[i] < v[bi] || (v[i] == v[bi] && i < bi)))) {
                         bd = d;
                         bi = i;
@@ -201,7 +221,7 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
     }
     *iters = it < max_iter ? it + 1 : max_iter;
     if (!*strict)
-        for (int64_t i = 0; i < n; ++i) lab[i] = assign(v[i], cen, k);
+        for (int64_t i = 0; i < n; ++i) lab[i] = assign(v[i], cen, k, D->g);
     /* inertia from exact per-cluster sums of q and q^2 */
     int64_t s1[8] = {0};
     u128 s2[8] = {0};
@@ -215,8 +235,12 @@ static double run_one(const kdata *D, int k, int64_t first, const double *u, int
     double I = 0;
     for (int j = 0; j < k; ++j) {
         if (!nn[j]) continue;
-        const double cs = ldexp(cen[j], D->s);
-        I += ((double)s2[j] - 2.0 * cs * (double)s1[j]) + (double)nn[j] * cs * cs;
+        /* sum (q - c)^2 = sum (q - mean)^2 + n (c - mean)^2; the first term as the exact integer
+         * n sum(q^2) - sum(q)^2 (below 2^122) over n: a mean far above the spread cancels nothing */
+        const uint64_t a1 = s1[j] < 0 ? -(uint64_t)s1[j] : (uint64_t)s1[j];
+        const u128 nw = (u128)(uint64_t)nn[j] * s2[j] - (u128)a1 * a1;
+        const double dm = ldexp(cen[j], D->s) - (double)s1[j] / (double)nn[j];
+        I += (double)nw / (double)nn[j] + (double)nn[j] * dm * dm;
     }
     free(old);
     return ldexp(I, -2 * D->s);
@@ -233,11 +257,27 @@ static int same_partition(const int32_t *a, const int32_t *b, int64_t n, int k) 
     return 1;
 }
 
-EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, int k, int n_init, int max_iter,
-                            const int64_t *first, const double *draws, int32_t *labels, double *centers,
-                            int64_t *info) {
+/* the potential scale S and the factor g (header: value domain) */
+static void pot_scale(double r, int *S, double *g) {
+    int e = 0;
+    const double f = frexp(r > 0 ? r : 1.0, &e);
+    const int e2 = 2 * e - (f * f < 0.5);
+    const int normal = r >= 0x1p-481 && r < 0x1p512;
+    *S = normal ? 61 - e2 : 60;
+    *g = normal ? 1.0 : 0.0;
+}
+
+EXPORT int oracle_kmeans_sk_runs(const double *x, const uint8_t *valid, int64_t n, int k, int n_init, int max_iter,
+                                 const int64_t *first, const double *draws, int32_t *labels, double *centers,
+                                 int64_t *info, int64_t *runs) {
     int64_t nv = 0;
-    for (int64_t i = 0; i < n; ++i) nv += !valid || valid[i];
+    for (int j = 0; j < 4; ++j) info[j] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (valid && !valid[i]) continue;
+        if (!(fabs(x[i]) <= 0x1p1022)) return 1;
+        nv += 1;
+    }
+    if (nv >= 1 && nv < k) return 2;
     double *v = (double *)malloc(sizeof(double) * (size_t)(nv ? nv : 1));
     double mn = INFINITY, mx = -INFINITY, amax = 0;
     nv = 0;
@@ -248,7 +288,6 @@ EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, in
         mx = x[i] > mx ? x[i] : mx;
         amax = fabs(x[i]) > amax ? fabs(x[i]) : amax;
     }
-    for (int j = 0; j < 4; ++j) info[j] = 0;
     if (nv == 0) {
         for (int64_t i = 0; i < n; ++i) labels[i] = -1;
         free(v);
@@ -258,10 +297,7 @@ EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, in
     D.n = nv;
     D.v = v;
     D.s = oracle_kmeans_scale(amax, nv);
-    const double r = mx - mn, R2 = r * r;
-    int e = 0;
-    frexp(R2 > 0 ? R2 : 1.0, &e);
-    D.S = 61 - e;
+    pot_scale(mx - mn, &D.S, &D.g);
     /* tol = 1e-4 * var(x) from exact sums */
     int64_t t1 = 0;
     u128 t2 = 0;
@@ -270,8 +306,11 @@ EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, in
         t1 += q;
         t2 += (u128)((__int128)q * q);
     }
-    const double m1 = (double)t1 / (double)nv, m2 = (double)t2 / (double)nv;
-    const double var = ldexp(m2 - m1 * m1, -2 * D.s);
+    /* n^2 var = n sum(q^2) - sum(q)^2, exact below 2^122 (|q| <= 2^(61 - ceil(log2 n))): the
+     * difference is taken in integers, so a mean far above the spread cancels nothing */
+    const uint64_t a1 = t1 < 0 ? -(uint64_t)t1 : (uint64_t)t1;
+    const u128 nvar = (u128)(uint64_t)nv * t2 - (u128)a1 * a1;
+    const double var = ldexp((double)nvar / (double)nv / (double)nv, -2 * D.s);
     const double tol = var * 1e-4;
     const int nt = 2 + (int)log((double)k);
     int32_t *lab = (int32_t *)malloc(sizeof(int32_t) * (size_t)nv);
@@ -280,8 +319,14 @@ EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, in
     int have = 0, reloc = 0;
     for (int r0 = 0; r0 < n_init; ++r0) {
         int it = 0, strict = 0;
+        const int reloc0 = reloc;
         const double I = run_one(&D, k, first[r0], draws + (size_t)r0 * (k - 1) * nt, nt, max_iter, tol, lab, cen,
                                  &it, &strict, &reloc);
+        if (runs) {
+            runs[3 * r0] = it;
+            runs[3 * r0 + 1] = strict;
+            runs[3 * r0 + 2] = reloc - reloc0;
+        }
         if (!have || (I < binert && !same_partition(lab, best, nv, k))) {
             have = 1;
             binert = I;
@@ -300,4 +345,10 @@ EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, in
     free(lab);
     free(best);
     return 0;
+}
+
+EXPORT int oracle_kmeans_sk(const double *x, const uint8_t *valid, int64_t n, int k, int n_init, int max_iter,
+                            const int64_t *first, const double *draws, int32_t *labels, double *centers,
+                            int64_t *info) {
+    return oracle_kmeans_sk_runs(x, valid, n, k, n_init, max_iter, first, draws, labels, centers, info, NULL);
 }

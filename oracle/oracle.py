@@ -384,10 +384,16 @@ def kmeans_draws(nv, k, n_init=10, seed=0):
 def kmeans_sk(x, k, valid=None, n_init=10, max_iter=300, seed=0):
     """sklearn KMeans(k, random_state=0, n_init=10).fit_predict(x.reshape(-1,1)) restated
     (kmeans_sk.c) -> labels (sklearn's cluster ids, -1 where not valid), centres, info
-    [winning run, its iterations, strict convergence, empty-cluster relocations]"""
+    [winning run, its iterations, strict convergence, empty-cluster relocations].
+    ValueError where sklearn raises one: a valid sample that is NaN or infinite (or above 2^1022
+    in magnitude), or 1 <= valid samples < k"""
+    return kmeans_sk_runs(x, k, valid, n_init, max_iter, seed)[:3]
+
+
+def kmeans_sk_runs(x, k, valid=None, n_init=10, max_iter=300, seed=0):
+    """kmeans_sk plus the per-run records: an (n_init, 3) array of Lloyd iterations, strict
+    convergence and empty-cluster relocations of every run, not only the winner"""
     xv = _c(x, np.float64).ravel()
-    if np.isnan(xv if valid is None else xv[_c(valid, np.uint8).ravel().astype(bool)]).any():
-        raise ValueError("Input contains NaN")          # sklearn's check_array
     vp = None
     nv = xv.size
     if valid is not None:
@@ -398,9 +404,14 @@ def kmeans_sk(x, k, valid=None, n_init=10, max_iter=300, seed=0):
     lab = np.zeros(xv.size, np.int32)
     cen = np.zeros(k, np.float64)
     info = np.zeros(4, np.int64)
-    lib().oracle_kmeans_sk(_p(xv), vp, I64(xv.size), k, n_init, max_iter, _p(first), _p(draws), _p(lab), _p(cen),
-                           _p(info))
-    return lab.reshape(np.shape(x)), cen, info
+    runs = np.zeros((n_init, 3), np.int64)
+    st = lib().oracle_kmeans_sk_runs(_p(xv), vp, I64(xv.size), k, n_init, max_iter, _p(first), _p(draws), _p(lab),
+                                     _p(cen), _p(info), _p(runs))
+    if st == 1:                                          # sklearn's check_array
+        raise ValueError("Input contains NaN or infinity, or a finite magnitude above 2^1022")
+    if st == 2:                                          # sklearn's _check_params_vs_input
+        raise ValueError("n_samples=%d should be >= n_clusters=%d" % (nv, k))
+    return lab.reshape(np.shape(x)), cen, info, runs
 
 
 # ---- a21/a22/a23 ---------------------------------------------------------------------
